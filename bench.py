@@ -23,8 +23,13 @@ One step = one pass of the hot path over the shard, everything from the raw byte
        occurrences are combined over the ranks in one all-gather and one all-reduce: qname.in_step is true at every N.)
 `value` = FASTQ bytes of all ranks / time, MAX over ranks.
 Besides the contract fields the JSON line carries `roofline` (pack kernel, HIP-event timed inside the
-timed region on the launch stream) and `cpu_baseline` (the faithful per-base Python loops of the
-oracle on one host core, on a bounded sample of the same input; rank 0, N = 1 only).
+timed region on the launch stream).  A plain run does nothing else: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs DIR) and the JSON line.  `--full` adds the legs that take runs or checks of their own: `cpu_baseline`
+(the faithful per-base Python loops of the oracle on one host core, on a bounded sample of the same input; rank 0,
+N = 1 only), the exact QNAME kernels against the step's columns, the step without the QNAME passes, `north_star_200M`,
+`sort_leg` and `end_to_end`.
+`--dump-outputs DIR`: rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB;
+the rows and QNAME columns of a fixed, seeded sample of the reads), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -88,6 +93,52 @@ def cpu_baseline(sample_bytes, n_sample, d):
     return out, (dna, qual)
 
 
+DUMP_BYTES = 60_000_000    # --dump-outputs: every file together stays below this (the limit is 64 MB)
+DUMP_SEED = 20261016       # the sample of reads whose rows and QNAME fields are written
+
+
+def dump_outputs(out_dir, ctx, state):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files (float32: bytes and codes; float64: counts and values)
+        shape.npy          reads, lines, bits per base / quality, variable lengths (0 / 1), bytes per DNA / QUAL row, shortest / longest read
+        pack_tables.npy    3 x 256: the DNA code, QUAL code and N quality code of every byte value (-1: none), i.e. the decisions
+        stats_counts.npy   256 x 256: the (base, quality) counts of the whole shard
+        sample_reads.npy   the read numbers (ascending) of a fixed, seeded sample of the reads, and of those reads:
+        dna_rows.npy, qual_rows.npy   the packed rows
+        qname_<i>.npy      the values of QNAME column i (a column of another kind: its bytes, one row per read)
+        qname_layout.npy   the bytes of the QNAME layout as JSON: prefix, suffix, separators, column descriptions
+    The sample is as large as the 64 MB allow and the same from run to run for the same arguments."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    d, p, hs, n = state['d'], state['params'], state['hs'], state['nreads']
+    cd, cq = d['dna_bytes_per_row'], d['quality_bytes_per_row']
+    out = {'shape': np.array([n, state['nlines'], d['bits_per_base'], d['bits_per_quality'], int(d['variable_read_lengths']), cd, cq,
+                              hs.len_min, hs.len_max], dtype=np.float64),
+           'pack_tables': np.stack([np.ctypeslib.as_array(p.dna_code), np.ctypeslib.as_array(p.qual_code),
+                                    np.ctypeslib.as_array(p.n_qual)]).astype(np.float32),
+           'stats_counts': np.asarray(hs.counts, dtype=np.float64)}
+    # (name, device tensor, bytes per read, dtype of one value per read or None: bytes)
+    per_read = [('dna_rows', state['dna'], cd, None), ('qual_rows', state['qual'], cq, None)]
+    if state.get('qname') is not None:
+        prefix, suffix, separators, columns, arrays = state['qname']
+        layout = json.dumps([prefix, suffix, separators, columns], sort_keys=True, default=str).encode()
+        out['qname_layout'] = np.frombuffer(layout, dtype=np.uint8).astype(np.float32)
+        for i, (c, a) in enumerate(zip(columns, arrays)):
+            dt = np.dtype(c['dtype']) if 'dtype' in c else None
+            if dt is None or dt.kind not in 'iu' or dt.itemsize != a.element_size(): dt = None
+            per_read.append(('qname_%d' % i, a, a.element_size(), dt))
+    row_bytes = 8 + sum(4 * w if dt is None else 8 for _, _, w, dt in per_read)
+    fixed = sum(a.nbytes for a in out.values()) + 1024 * (len(out) + len(per_read) + 1)          # (and the .npy headers)
+    k = min(n, (DUMP_BYTES - fixed) // row_bytes)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    out['sample_reads'] = idx.astype(np.float64)
+    idx_t = torch.from_numpy(idx).to(ctx.device)
+    for name, t, w, dt in per_read:
+        rows = t.reshape(-1).view(torch.uint8)[:n * w].view(n, w)[idx_t].cpu().numpy()
+        out[name] = rows.astype(np.float32) if dt is None else rows.view(dt).reshape(k).astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -95,14 +146,19 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--reads', type=int, default=10_000_000, help='reads per GPU (default: BASELINE configs[1])')
     ap.add_argument('--length', type=int, default=150)
-    ap.add_argument('--cpu-sample', type=int, default=250_000, help='reads timed on the host for cpu_baseline (0 = skip; the default is ~12 s of the Python port on one core)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline figure: cpu_baseline, the exact QNAME kernels against the step, the step '
+                         'without the QNAME passes, north_star_200M, sort_leg and end_to_end (each as set by the options below)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, under 64 MB)')
+    ap.add_argument('--cpu-sample', type=int, default=250_000, help='--full: reads timed on the host for cpu_baseline (0 = skip; the default is ~12 s of the Python port on one core)')
     ap.add_argument('--north-star-reads', type=int, default=200_000_000,
-                    help='N = 1: the same step timed once more at the north_star\'s single-GPU size (200 M x 150 bp), reported as '
+                    help='--full, N = 1: the same step timed once more at the north_star\'s single-GPU size (200 M x 150 bp), reported as '
                          'north_star_200M; 0 = skip')
     ap.add_argument('--sort-reads', type=int, default=200_000_000,
-                    help='reads of the global --sort legs over ALL GPUs (strong scaling: 200 M / N per GPU; BASELINE configs[3] is 200 M over '
+                    help='--full: reads of the global --sort legs over ALL GPUs (strong scaling: 200 M / N per GPU; BASELINE configs[3] is 200 M over '
                          '8 GPUs); 0 = skip')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end record (N = 1: the CLI on a tmpfs file of the same workload, both ways)')
+    ap.add_argument('--no-e2e', action='store_true', help='--full: skip the end-to-end record (N = 1: the CLI on a tmpfs file of the same workload, both ways)')
     ap.add_argument('--force-dist', action='store_true', help='initialise the process group and run the collectives even with one rank')
     ap.add_argument('--multi-pass', action='store_true',
                     help='round 1\'s step: census -> index -> statistics -> decisions -> pack, three reads of the stream (the default '
@@ -299,7 +355,7 @@ def main():
                 e1.record()
                 kernel = 'pack_tile_kernel'
             if timed: pack_events.append((e0, e1, kernel))
-            state.update(dna=dna, qual=qual, bad=bad, d=d, nreads=nreads, nlines=nlines, ls=ls, params=p, qname=qres, qname_path=qpath)
+            state.update(dna=dna, qual=qual, bad=bad, d=d, hs=hs, nreads=nreads, nlines=nlines, ls=ls, params=p, qname=qres, qname_path=qpath)
 
         for _ in range(warmup):
             step(False)
@@ -310,7 +366,8 @@ def main():
         fence()
         dt = time.perf_counter() - t0
         indexed = state['ls'] is not None                                   # did the step expand the record index?
-        if state['ls'] is None: state['ls'] = ops.index_lines(ctx, d_buf, ops.count_lines(ctx, d_buf))     # (for the checks below, outside the timed region)
+        if state['ls'] is None and args.full:
+            state['ls'] = ops.index_lines(ctx, d_buf, ops.count_lines(ctx, d_buf))     # (for the --full checks, outside the timed region)
         total_bytes, total_reads = fastq_bytes, state['nreads']
         if use_dist:
             t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
@@ -362,9 +419,11 @@ def main():
                 'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic, 'algorithmic_bytes_per_launch': int(m['algo_bytes']),
                 'avg_launch_ms': round(m['pack_ms'], 4)}
 
-    m = run_encode(args.reads, args.steps, args.warmup, True)
+    m = run_encode(args.reads, args.steps, args.warmup, args.full)
     state, d, nreads, fastq_bytes, kernel = m['state'], m['d'], m['nreads'], m['fastq_bytes'], m['kernel']
     two_reads = kernel.startswith('pack_tile_kernel<STATS')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, state)
 
     def measured_traffic(workload, reads, form):
         """HBM bytes per launch of the step's pack kernel from the PMC passes on record (profiles/pack_stats_traffic.json: rocprofv3 --pmc FETCH_SIZE /
@@ -396,8 +455,7 @@ def main():
         'ms_per_step': round(m['dt_step'] * 1e3, 3), 'higher_is_better': True, 'scaling': 'weak',
         'vs_baseline': None, 'dtype': 'u8', 'data': 'synthetic',
         'reads_per_s': round(m['total_reads'] / m['dt_step'], 1),
-        'qname': {'in_step': bool(qname_in_step), 'path': state.get('qname_path'),
-                  'exact_kernels_ms': None if m['qname_exact_ms'] is None else round(m['qname_exact_ms'], 3)},
+        'qname': {'in_step': bool(qname_in_step), 'path': state.get('qname_path')},
         'config': {'workload': ('BASELINE configs[1]: %d x %dbp synth-v1 FASTQ per GPU (%.3f GB), --sort None --raw DNA QUAL QNAME '
                                 '--pattern 0.1 0.1; step = census + index + stats + decisions + %d-bit DNA / %d-bit QUAL pack%s%s'
                                 % (nreads, args.length, fastq_bytes / 1e9, d['bits_per_base'], d['bits_per_quality'], mode, qmode)) if args.workload == 'cfg2' else
@@ -413,6 +471,16 @@ def main():
         'roofline': roofline_of(m, traffic),
     }
 
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), file=json_out, flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+
+    if not args.full:                   # a plain run: the headline figure and nothing else
+        return finish()
+    # ---- --full: the legs beyond the headline figure
+    result['qname']['exact_kernels_ms'] = None if m['qname_exact_ms'] is None else round(m['qname_exact_ms'], 3)
     if rank == 0 and world == 1 and args.cpu_sample > 0:
         ns = min(args.cpu_sample, nreads)
         end = int(state['ls'][4 * ns].item())
@@ -466,11 +534,7 @@ def main():
         except OSError as e:                                   # (no room on the tmpfs of this box: say so instead of failing the line)
             result['end_to_end'] = {'skipped': '%s: %s' % (type(e).__name__, e)}
         torch.cuda.empty_cache()
-
-    if rank == 0:
-        print(json.dumps(result), file=json_out, flush=True)
-    if use_dist:
-        dist.destroy_process_group()
+    finish()
 
 
 def end_to_end(ctx, args):

@@ -231,7 +231,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, UQ_DIST_BACKEND='gloo', PYTHONPATH=REPO)
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                           '--master-port', str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                          '--reads', '200000', '--sort-reads', '150000'], env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                          '--full', '--reads', '200000', '--sort-reads', '150000'], env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode(errors='replace')[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -245,6 +245,60 @@ def test_bench_two_ranks_rehearsal():
     assert sl['reads_total'] == 150000 and sl['reads_per_gpu'] == 75000
     for leg in ('sort_qual_raw', 'sort_dna_keyed'):
         assert sl[leg]['ms'] > 0 and 75000 <= sl[leg]['largest_shard_after_exchange'] <= 100000, sl[leg]
+
+
+def _bench_plain(out_dir, n):
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--reads', str(n),
+                          '--dump-outputs', str(out_dir)], cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert out.returncode == 0, out.stderr.decode(errors='replace')[-2000:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def _check_dump(out_dir, n, seed=20261005, length=150):
+    """bench.py --dump-outputs against the C oracle (rows, counts, decisions) and the host QNAME analysis, on the same synthetic input."""
+    import numpy as np
+    import oracle_c
+    from uq_amd import qname
+    files = sorted(os.listdir(out_dir))
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in files) <= 64_000_000
+    got = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()), {k: a.dtype for k, a in got.items()}
+    host = synth.fastq_array(synth.Spec(seed, length), n)
+    hls = oracle_c.index_lines(host)
+    ref = oracle_c.stats(host, hls, 0, n)
+    d = O.decide(O.histogram_to_static_qualities(ref['counts'], ref['first_seen']), ref['len_min'], ref['len_max'])
+    rd, rq, _ = oracle_c.pack(host, hls, 0, n, d['bases'], d['qualities'], d['N_qual'], d['bits_per_base'], d['bits_per_quality'],
+                              d['variable_read_lengths'], d['dna_bytes_per_row'], d['quality_bytes_per_row'])
+    assert got['shape'].tolist() == [n, 4 * n, d['bits_per_base'], d['bits_per_quality'], int(d['variable_read_lengths']),
+                                     d['dna_bytes_per_row'], d['quality_bytes_per_row'], ref['len_min'], ref['len_max']]
+    assert np.array_equal(got['stats_counts'], np.asarray(ref['counts'], dtype=np.float64).reshape(256, 256))
+    codes = got['pack_tables']
+    assert ''.join(chr(c) for c in np.flatnonzero(codes[0] >= 0)) == d['bases'] and ''.join(chr(c) for c in np.flatnonzero(codes[1] >= 0)) == d['qualities']
+    idx = got['sample_reads'].astype(np.int64)
+    assert idx.size > 0 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n and np.array_equal(idx, got['sample_reads'])
+    assert np.array_equal(got['dna_rows'], rd[idx].astype(np.float32)) and np.array_equal(got['qual_rows'], rq[idx].astype(np.float32))
+    prefix, suffix, separators, columns, arrays = qname.analyse(qname.qname_lines(host, hls, n))
+    assert json.loads(got['qname_layout'].astype(np.uint8).tobytes()) == json.loads(json.dumps([prefix, suffix, separators, columns], sort_keys=True, default=str))
+    for i, a in enumerate(arrays):
+        assert np.array_equal(got['qname_%d' % i], np.asarray(a)[idx].astype(np.float64)), i
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain bench.py run does the headline figure and nothing else; --dump-outputs writes what its last step computed (a seeded sample of
+    the rows and QNAME columns, the counts, the decisions) -- equal to the oracle's, and the same in a second run."""
+    n = 200_000
+    r = _bench_plain(tmp_path / 'a', n)
+    assert r['steps'] == 3 and r['warmup'] == 1 and r['ms_per_step'] > 0 and r['value'] > 0 and r['unit'] == 'MB/s'
+    assert r['higher_is_better'] is True and r['dtype'] == 'u8' and r['config']['reads_per_gpu'] == n
+    assert not {'cpu_baseline', 'north_star_200M', 'sort_leg', 'end_to_end'} & set(r)              # the --full legs
+    assert set(r['qname']) == {'in_step', 'path'}
+    _check_dump(tmp_path / 'a', n)
+    _bench_plain(tmp_path / 'b', n)
+    assert sorted(os.listdir(tmp_path / 'a')) == sorted(os.listdir(tmp_path / 'b'))
+    for f in os.listdir(tmp_path / 'a'):
+        assert open(tmp_path / 'a' / f, 'rb').read() == open(tmp_path / 'b' / f, 'rb').read(), f
 
 
 def _run_sharded_expect_error(world, inp, out, flags, timeout=120):

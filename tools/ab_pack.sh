@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out; mkdir -p $OUT/$(dirname $tag)
 for round in 1 2; do
   for v in "$@"; do
     lib=$R/uq_amd/_variants/libuqhip_$v.so; [ "$v" = main ] && lib=$R/uq_amd/libuqhip.so
-    UQ_LIB_PATH=$lib timeout -k 10 300 python3 $R/bench.py --steps 20 --warmup 3 --no-e2e --cpu-sample 0 --north-star-reads 0 --sort-reads 0 > $OUT/${tag}_$v.json 2> $OUT/${tag}_$v.err || { echo "$v FAILED" >> $OUT/${tag}_ab.txt; exit 1; }
+    UQ_LIB_PATH=$lib timeout -k 10 300 python3 $R/bench.py --steps 20 --warmup 3 --full --no-e2e --cpu-sample 0 --north-star-reads 0 --sort-reads 0 > $OUT/${tag}_$v.json 2> $OUT/${tag}_$v.err || { echo "$v FAILED" >> $OUT/${tag}_ab.txt; exit 1; }
     python3 - $OUT/${tag}_$v.json $v $round >> $OUT/${tag}_ab.txt <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

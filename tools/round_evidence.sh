@@ -4,7 +4,7 @@
 tag=$1
 R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out/$tag; mkdir -p $OUT
 K='pack_tile_kernel'
-B="--cpu-sample 0 --north-star-reads 0 --sort-reads 0 --no-e2e"
+B="--full --cpu-sample 0 --north-star-reads 0 --sort-reads 0 --no-e2e"
 set -e
 tools/pmc_traffic.sh $tag/bench_10M "$K" bench.py $B --steps 3 --warmup 1 > $OUT/a.log 2>&1; echo "10M traffic done"
 tools/pmc_sq.sh $tag/bench_10M "$K" bench.py $B --steps 3 --warmup 1 > $OUT/b.log 2>&1; echo "10M sq done"
