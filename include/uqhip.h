@@ -451,6 +451,39 @@ typedef struct uq_synth_spec {
 int uq_synth_size(uq_ctx* ctx, const uq_synth_spec* h_spec, uint64_t first, uint64_t n, uint64_t* h_bytes);
 int uq_synth_fastq(uq_ctx* ctx, const uq_synth_spec* h_spec, uint64_t first, uint64_t n, uint8_t* d_out, uint64_t capacity);
 
+/* ---- gzip input (an extension: the reference reads plain FASTQ only).  A BGZF file (what `bgzip` writes) is a chain of independent
+ * gzip members, each with its compressed size in a `BC` extra subfield (BSIZE) and at most 64 KiB of output: they inflate in parallel
+ * on the device.  Any other gzip is inflated on the host.
+ * uq_gzip_scan: walks the RFC 1952 member headers of h_buf[0, nbytes) (FEXTRA, FNAME, FCOMMENT, FHCRC).  *h_kind:
+ *   UQ_GZIP_BGZF       every member carries BSIZE (the 28-byte EOF block and other empty members included): h_members[k] for all of them,
+ *                      out_offset = the 64-bit prefix sum of ISIZE, *h_total_out = the inflated size;
+ *   UQ_GZIP_OTHER      a member without BSIZE: the walk stops at it (its end is known only by inflating it); it is the last entry, with
+ *                      comp_bytes = the rest of the input and isize = crc32 = 0;
+ *   UQ_GZIP_MALFORMED  a truncated header or member, no magic, a method other than deflate, reserved flags, a bad header CRC, a BSIZE past
+ *                      the end, ISIZE > 65536 in a BGZF member: *h_bad_offset = the member's offset, the message in uq_last_error().
+ * h_members = NULL counts only (*h_nmembers); otherwise it holds `capacity` entries.  Returns 0 whatever the class. */
+#define UQ_GZIP_BGZF 1
+#define UQ_GZIP_OTHER 2
+#define UQ_GZIP_MALFORMED 3
+typedef struct uq_gzip_member {
+    uint64_t data_offset;       /* first byte of the member's deflate data in the input */
+    uint64_t comp_bytes;        /* deflate bytes (BSIZE + 1 - header - trailer) */
+    uint64_t out_offset;        /* where its output starts in the inflated file */
+    uint32_t isize;             /* trailer: output bytes */
+    uint32_t crc32;             /* trailer: CRC-32 of the output */
+} uq_gzip_member;
+int uq_gzip_scan(const uint8_t* h_buf, uint64_t nbytes, uq_gzip_member* h_members, uint64_t capacity, uint64_t* h_nmembers,
+                 uint64_t* h_total_out, int* h_kind, uint64_t* h_bad_offset);
+/* uq_inflate_members: every member of d_members[0, nmembers) (a uq_gzip_scan table, in device memory) inflated from d_comp (the whole
+ * compressed input, comp_bytes) into d_out[out_offset, out_offset + isize), one wave per member, its length and CRC-32 checked on the
+ * device.  d_status[k] = 0, or the UQ_INF_* code (uq_amd/csrc/inflate_core.h) that stopped member k; a member that fails writes nothing
+ * to d_out.  Reads stay inside [data_offset, data_offset + comp_bytes) and writes inside [out_offset, out_offset + isize), whatever the
+ * bytes; a member that is not inside d_comp / d_out gets UQ_INF_TOO_LARGE.
+ * uq_inflate_member_host: the same decoder on one member's deflate data on the CPU (h_out holds isize <= 65536 bytes): *h_status as above. */
+int uq_inflate_members(uq_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, const uq_gzip_member* d_members, uint64_t nmembers,
+                       uint8_t* d_out, uint64_t out_bytes, uint32_t* d_status);
+int uq_inflate_member_host(const uint8_t* h_comp, uint64_t comp_bytes, uint8_t* h_out, uint64_t isize, uint32_t crc32, uint32_t* h_status);
+
 #ifdef __cplusplus
 }
 #endif

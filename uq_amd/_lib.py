@@ -58,6 +58,11 @@ class QnameFused(C.Structure):
                 ('nreads', C.c_uint64), ('thresholds', C.c_uint64 * 24), ('counts', (C.c_uint64 * 24) * 8)]
 
 
+class GzipMember(C.Structure):
+    _fields_ = [('data_offset', C.c_uint64), ('comp_bytes', C.c_uint64), ('out_offset', C.c_uint64), ('isize', C.c_uint32),
+                ('crc32', C.c_uint32)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -145,6 +150,9 @@ SIGNATURES = {
     'uq_decode_fastq': [_vp, _P(EmitParams), _P(UnpackParams), _P(_vp), _P(_vp), _P(_vp), _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _P(_u64), _P(_u64)],
     'uq_synth_size': [_vp, _P(SynthSpec), _u64, _u64, _P(_u64)],
     'uq_synth_fastq': [_vp, _P(SynthSpec), _u64, _u64, _vp, _u64],
+    'uq_gzip_scan': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u64), _P(_int), _P(_u64)],
+    'uq_inflate_members': [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp],
+    'uq_inflate_member_host': [_vp, _u64, _vp, _u64, _u32, _P(_u32)],
 }
 
 _lib = None

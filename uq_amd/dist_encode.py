@@ -435,9 +435,15 @@ class ShardedSession(Session):
 
 
 def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if not args.decode and args.input and os.path.isfile(args.input):
+        from .ops import is_gzip
+        if is_gzip(args.input):
+            # before any device or process-group set-up: every rank reads the same two bytes and stops alike
+            print('ERROR: the sharded encoder reads plain FASTQ only; encode gzip input on one GPU (python -m uq_amd.uq) or decompress it first')
+            return 1
     import torch
     import torch.distributed as dist
-    args = build_parser().parse_args(argv)
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     backend = os.environ.get('UQ_DIST_BACKEND', 'nccl')

@@ -85,6 +85,59 @@ class Staging:
             os.close(fd)
         return d
 
+    # ------------------------------------------------------------------ gzip file -> HBM (host inflate)
+    def gzip_to_device(self, path, read_chunk=1 << 20):
+        """A gzip file that is not BGZF (one member, or members without a BSIZE field), inflated on the host with zlib, member after
+        member, the output streamed through the pinned buffers into HBM: the host holds one read and the pinned buffers, never the
+        file.  Returns the uint8 device tensor of the inflated bytes.  The inflated size is known only at the end, so the device buffer
+        grows by doubling (a copy inside HBM).  zlib.error / EOFError for a damaged or truncated stream."""
+        import zlib
+        ctx = self.ctx
+        pin, pnp, ev = self._buffers()
+        st = {'d': ctx.empty(max(self.chunk, 4 * os.path.getsize(path))), 'size': 0, 'fill': 0, 'k': 0}
+
+        def flush():
+            n, k = st['fill'], st['k']
+            if n == 0: return
+            d, size = st['d'], st['size']
+            if size + n > d.numel():
+                grown = ctx.empty(max(2 * d.numel(), size + n))
+                grown[:size].copy_(d[:size])
+                st['d'] = d = grown
+            d[size:size + n].copy_(pin[k][:n], non_blocking=True)
+            ev[k].record()
+            st['size'], st['fill'], st['k'] = size + n, 0, (k + 1) % self.nbuf
+            ev[st['k']].synchronize()                  # the next buffer's previous copy has left the host
+
+        def put(out):
+            n = len(out)
+            if n:
+                pnp[st['k']][st['fill']:st['fill'] + n] = np.frombuffer(out, dtype=np.uint8)
+                st['fill'] += n
+                if st['fill'] == self.chunk: flush()
+
+        dec, fed = zlib.decompressobj(31), False
+        with open(path, 'rb') as f:
+            while True:
+                buf = f.read(read_chunk)
+                if not buf: break
+                fed = True
+                while True:
+                    out = dec.decompress(buf, self.chunk - st['fill'])
+                    put(out)
+                    buf = dec.unconsumed_tail
+                    if dec.eof:                                 # the next member starts in what is left
+                        buf = dec.unused_data
+                        dec, fed = zlib.decompressobj(31), bool(buf)
+                        if not buf: break
+                    elif not buf and not out:
+                        break
+        if fed and not dec.eof:
+            raise EOFError('%s: the gzip stream ends inside a member' % path)
+        flush()
+        for e in ev: e.synchronize()
+        return st['d'][:st['size']]
+
     # ------------------------------------------------------------------ HBM -> file
     def device_to_fd(self, tensor, fd, offset):
         """Writes the bytes of a device tensor to `fd` at `offset` (pwrite).  Returns the byte count."""

@@ -642,3 +642,62 @@ def synth_fastq(ctx, spec, first, n):
     out = t.empty(nbytes.value, dtype=t.uint8, device=ctx.device)
     call('uq_synth_fastq', ctx.h, C.byref(cs), first, n, _p(out), nbytes.value)
     return out
+
+
+# ------------------------------------------------------------------ gzip input (an extension: BGZF members inflate on the device)
+GZIP_BGZF, GZIP_OTHER, GZIP_MALFORMED = 1, 2, 3
+GZIP_MEMBER = np.dtype([('data_offset', '<u8'), ('comp_bytes', '<u8'), ('out_offset', '<u8'), ('isize', '<u4'), ('crc32', '<u4')])
+INFLATE_STATUS = {1: 'deflate data runs past the end of the member', 2: 'invalid block type', 3: 'stored block length check failed',
+                  4: 'invalid code lengths set', 5: 'invalid code length repeat', 6: 'invalid Huffman code', 7: 'distance too far back',
+                  8: 'more output than the trailer\'s ISIZE', 9: 'less output than the trailer\'s ISIZE', 10: 'CRC-32 mismatch',
+                  11: 'too many length or distance symbols', 12: 'member larger than 64 KiB or outside the input'}
+
+
+def is_gzip(path):
+    """Content sniff: gzip files start with 1f 8b (plain FASTQ starts with '@')."""
+    with open(path, 'rb') as f:
+        return f.read(2) == b'\x1f\x8b'
+
+
+def gzip_scan(buf):
+    """uq_gzip_scan over a host uint8 array (a memmap will do: only the headers are touched).  Returns (kind, members, total_out, error):
+    members a GZIP_MEMBER array; error = (message, member offset) when kind is GZIP_MALFORMED, else None."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 else buf
+    n, total, kind, bad = C.c_uint64(), C.c_uint64(), C.c_int(), C.c_uint64()
+    ptr = C.c_void_p(buf.ctypes.data if buf.size else 0)
+    call('uq_gzip_scan', ptr, buf.size, None, 0, C.byref(n), C.byref(total), C.byref(kind), C.byref(bad))
+    if kind.value == GZIP_MALFORMED:
+        return kind.value, np.zeros(0, GZIP_MEMBER), total.value, (load().uq_last_error().decode('utf-8', 'replace'), bad.value)
+    members = np.zeros(n.value, GZIP_MEMBER)
+    call('uq_gzip_scan', ptr, buf.size, C.c_void_p(members.ctypes.data), n.value, C.byref(n), C.byref(total), C.byref(kind), C.byref(bad))
+    return kind.value, members, total.value, None
+
+
+def inflate_members(ctx, d_comp, members, total_out, d_members=None):
+    """uq_inflate_members: the members (a GZIP_MEMBER array from gzip_scan) of the compressed bytes d_comp inflated into a fresh uint8 device
+    tensor of total_out bytes.  Returns (d_out, None), or (d_out, (member index, status)) for the first member that failed."""
+    t = ctx.torch
+    out = t.empty(int(total_out), dtype=t.uint8, device=ctx.device)
+    n = len(members)
+    if n == 0:
+        return out, None
+    if d_members is None:
+        d_members = ctx.to_device(np.ascontiguousarray(members).view(np.uint8))
+    st = t.zeros(n, dtype=t.int32, device=ctx.device)
+    call('uq_inflate_members', ctx.h, _p(d_comp), d_comp.numel(), _p(d_members), n, _p(out), out.numel(), _p(st))
+    bad = t.nonzero(st).flatten()[:1].cpu()
+    if bad.numel():
+        k = int(bad[0])
+        return out, (k, int(st[k]))
+    return out, None
+
+
+def inflate_member_host(data, isize, crc32):
+    """uq_inflate_member_host: one member's raw deflate bytes through the device decoder's code on the CPU.  Returns (status, bytes)."""
+    data = bytes(data)
+    src = np.frombuffer(data, dtype=np.uint8)
+    out = np.zeros(max(int(isize), 1), dtype=np.uint8)
+    st = C.c_uint32()
+    call('uq_inflate_member_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), int(isize),
+         int(crc32) & 0xFFFFFFFF, C.byref(st))
+    return st.value, out[:int(isize)].tobytes()

@@ -135,6 +135,7 @@ class Session:
         """Read the FASTQ, put it in HBM, build the record index.  Replaces `wc -l` + line iteration."""
         ops, ctx = self.ops, self.ctx
         if os.path.getsize(path) == 0: error('ERROR: empty input')
+        if ops.is_gzip(path): return self.load_gzip(path)
         self.path, self._host = path, None
         # pinned, chunked, file reads overlapped with the PCIe copies; the newline census of a chunk is queued right behind its
         # copy (row f2), so that only the scan of the per-tile counts is left when the last byte lands
@@ -146,6 +147,33 @@ class Session:
         chunked = self.io.chunk % (16 << 10) == 0
         d_buf = self.io.file_to_device(path, on_chunk=on_chunk if chunked else None)
         self.load_device(d_buf, census=census.get('c'))
+
+    def load_gzip(self, path):
+        """gzip input (an extension: the reference reads plain text only), recognised by its magic bytes.  BGZF (every member carries its
+        compressed size): the compressed file goes to HBM, the member headers are walked on the host, every member inflates on the device
+        into its slice of one buffer (uq_inflate_members).  Any other gzip inflates on the host (zlib), streamed to HBM.  Then load_device."""
+        ops, ctx = self.ops, self.ctx
+        kind, members, total, err = ops.gzip_scan(np.memmap(path, dtype=np.uint8, mode='r'))
+        if kind == ops.GZIP_MALFORMED: error('ERROR: %s is not a readable gzip file: %s' % (path, err[0]))
+        self.path, self._host = None, None             # the file holds compressed bytes: the host copy (`host`) comes from d_buf
+        if kind == ops.GZIP_BGZF:
+            self.gzip_path = 'BGZF, %d members inflated on the device' % len(members)
+            d_comp = self.io.file_to_device(path)
+            d_buf, bad = ops.inflate_members(ctx, d_comp, members, total)
+            del d_comp
+            if bad is not None:
+                k, st = bad
+                error('ERROR: %s: gzip member %d (deflate data at byte %d): %s' % (path, k, int(members[k]['data_offset']),
+                                                                                  ops.INFLATE_STATUS.get(st, 'status %d' % st)))
+        else:
+            self.gzip_path = 'gzip inflated on the host'
+            import zlib
+            try:
+                d_buf = self.io.gzip_to_device(path)
+            except (zlib.error, EOFError) as e:
+                error('ERROR: %s is not a readable gzip file: %s' % (path, e))
+        if d_buf.numel() == 0: error('ERROR: empty input')
+        self.load_device(d_buf)
 
     def load_device(self, d_buf, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
