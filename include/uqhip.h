@@ -484,6 +484,23 @@ int uq_inflate_members(uq_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, 
                        uint8_t* d_out, uint64_t out_bytes, uint32_t* d_status);
 int uq_inflate_member_host(const uint8_t* h_comp, uint64_t comp_bytes, uint8_t* h_out, uint64_t isize, uint32_t crc32, uint32_t* h_status);
 
+/* ---- BGZF output (an extension: the reference writes plain FASTQ only).  The deflate compressor is uq_amd/csrc/deflate_core.h: one
+ * dynamic-Huffman block per 65 280-byte input block (a stored block where that is smaller), so every member is at most 65 311 bytes; a
+ * member's bytes depend on its input bytes only.
+ * uq_bgzf_bound: *h_bound = the output capacity uq_bgzf_compress needs for nbytes of input (EOF member included). */
+int uq_bgzf_bound(uint64_t nbytes, uint64_t* h_bound);
+/* uq_bgzf_compress: d_in[0, nbytes) (device) as a BGZF stream into d_out (device, out_capacity bytes): one member per 65 280 bytes of input,
+ * compressed one workgroup per block, in chunks of blocks (the workspace, from the context's scratch pool, is bounded by the chunk); the
+ * members are placed at 64-bit offsets.  flags & UQ_BGZF_EOF: the 28-byte BGZF EOF member is appended.  *h_out_bytes = the bytes written.
+ * A block that fails, or a capacity that is too small, is an error naming the block.  Synchronises the context's stream. */
+#define UQ_BGZF_EOF 1u
+int uq_bgzf_compress(uq_ctx* ctx, const uint8_t* d_in, uint64_t nbytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* h_out_bytes,
+                     uint32_t flags);
+/* uq_bgzf_compress_block_host: the same compressor on the CPU, on one block (nbytes <= 65 280): h_out[0, capacity) receives the member,
+ * *h_out_bytes = its size.  *h_status = 0, 1 (the member needs more than `capacity` bytes: nothing but zeros written) or 2 (nbytes too large). */
+int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
+                                uint32_t* h_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,9 @@ SIGNATURES = {
     'uq_gzip_scan': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u64), _P(_int), _P(_u64)],
     'uq_inflate_members': [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp],
     'uq_inflate_member_host': [_vp, _u64, _vp, _u64, _u32, _P(_u32)],
+    'uq_bgzf_bound': [_u64, _P(_u64)],
+    'uq_bgzf_compress': [_vp, _vp, _u64, _vp, _u64, _P(_u64), _u32],
+    'uq_bgzf_compress_block_host': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32)],
 }
 
 _lib = None

@@ -392,8 +392,12 @@ class ShardedSession(Session):
             else: n = self.member_rows(members, 'DNA.key')
             lo, hi = n * self.rank // self.world, n * (self.rank + 1) // self.world
             DNA, QUAL, d_cols = self.load_tables(members, config, rows=(lo, hi))
-            if hi > lo: return self.decode_text(config, DNA, QUAL, d_cols), lo, n
-            return self.ctx.torch.empty(0, dtype=self.ctx.torch.uint8, device=self.ctx.device), lo, n
+            if hi > lo: text = self.decode_text(config, DNA, QUAL, d_cols)
+            else: text = self.ctx.torch.empty(0, dtype=self.ctx.torch.uint8, device=self.ctx.device)
+            if getattr(self.args, 'bgzf', False):
+                # every rank deflates its own text into whole members; the last one appends the EOF member
+                text = self.ops.bgzf_compress(self.ctx, text, eof=self.rank == self.world - 1)
+            return text, lo, n
         text, lo, n = self.guarded(my_text, 'decoding ' + str(self.args.input))
         shard = uqdist.Shard(self.be, lo, n, self.group)
         sizes = shard.gather_ints(int(text.numel()))

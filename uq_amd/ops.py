@@ -701,3 +701,43 @@ def inflate_member_host(data, isize, crc32):
     call('uq_inflate_member_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), int(isize),
          int(crc32) & 0xFFFFFFFF, C.byref(st))
     return st.value, out[:int(isize)].tobytes()
+
+
+# ------------------------------------------------------------------ BGZF output (an extension: members deflated on the device)
+BGZF_BLOCK = 65280
+DEFLATE_STATUS = {1: 'the member needs more than the output capacity', 2: 'more than 65 280 input bytes'}
+
+
+def bgzf_bound(nbytes):
+    """uq_bgzf_bound: the output capacity bgzf_compress needs for nbytes of input."""
+    out = C.c_uint64()
+    call('uq_bgzf_bound', int(nbytes), C.byref(out))
+    return out.value
+
+
+def bgzf_compress(ctx, d_text, eof=True):
+    """uq_bgzf_compress: the uint8 device tensor d_text as a BGZF stream (one member per 65 280 bytes, deflated on the device, plus the EOF
+    member when `eof`).  Returns a uint8 device tensor of exactly the stream's bytes."""
+    t = ctx.torch
+    n = d_text.numel()
+    out = t.empty(bgzf_bound(n), dtype=t.uint8, device=ctx.device)
+    nout = C.c_uint64()
+    call('uq_bgzf_compress', ctx.h, _p(d_text) if n else C.c_void_p(0), n, _p(out), out.numel(), C.byref(nout), 1 if eof else 0)
+    return out[:nout.value]
+
+
+def bgzf_block_host(data, capacity=None):
+    """uq_bgzf_compress_block_host: one block (<= 65 280 bytes) through the device compressor's code on the CPU.  Returns the member's
+    bytes; with `capacity`, returns (status, member size, the capacity's bytes) instead."""
+    data = bytes(data)
+    src = np.frombuffer(data, dtype=np.uint8)
+    cap = 65536 if capacity is None else int(capacity)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    nout, st = C.c_uint64(), C.c_uint32()
+    call('uq_bgzf_compress_block_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), cap,
+         C.byref(nout), C.byref(st))
+    if capacity is not None:
+        return st.value, nout.value, out[:cap].tobytes()
+    if st.value:
+        raise ValueError('bgzf_block_host: %s' % DEFLATE_STATUS.get(st.value, 'status %d' % st.value))
+    return out[:nout.value].tobytes()

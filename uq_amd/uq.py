@@ -64,6 +64,8 @@ def build_parser():
                         'packing speculatively with decisions guessed from the head of the file and verified afterwards (extension)')
     p.add_argument('--two-pass-decode', action='store_true', default=False,
                    help='decode through the fixed-pitch text arrays (uq_unpack + uq_emit_fastq) instead of the fused kernel (extension)')
+    p.add_argument('--bgzf', action='store_true', default=False,
+                   help='with --decode: write BGZF-compressed FASTQ (what bgzip writes), deflated on the GPU (extension)')
     return p
 
 
@@ -80,6 +82,7 @@ def validate_args(args):
         args.raw = set(args.raw)
         if 'none' in args.raw:
             args.raw.add(None); args.raw.discard('none')
+    if getattr(args, 'bgzf', False) and not args.decode: error('ERROR: --bgzf compresses decoded FASTQ: use it together with --decode')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     return args
 
@@ -822,18 +825,24 @@ class Session:
         DNA, QUAL, d_cols = self.load_tables(members, config)
         n = DNA[1]
         w = out.buffer if hasattr(out, 'buffer') else out
+        bgzf = getattr(self.args, 'bgzf', False)
         if self.device_text_possible(config):
-            # the text streams out through the pinned buffers
-            self.io.device_to_stream(self.decode_text(config, DNA, QUAL, d_cols), w)
+            # the text streams out through the pinned buffers (--bgzf: deflated on the device first)
+            text = self.decode_text(config, DNA, QUAL, d_cols)
+            self.io.device_to_stream(self.ops.bgzf_compress(ctx, text) if bgzf else text, w)
         else:
             seq, qt, ln = self.split_bits(DNA, QUAL, config)
             dmax = config['dna_max']
             S = ctx.to_numpy(seq).reshape(n, dmax); Q = ctx.to_numpy(qt).reshape(n, dmax); L = ctx.to_numpy(ln, np.uint32)
             cols = [ctx.to_numpy(c, np.dtype(cc['dtype'])) for c, cc in zip(d_cols, config['QNAME_columns'])]
             names = qname.decode_names(config, cols)
+            sink = io.BytesIO() if bgzf else w
             for r in range(n):
                 l = int(L[r])
-                w.write(names[r].encode('latin-1') + b'\n' + S[r, :l].tobytes() + b'\n+\n' + Q[r, :l].tobytes() + b'\n')
+                sink.write(names[r].encode('latin-1') + b'\n' + S[r, :l].tobytes() + b'\n+\n' + Q[r, :l].tobytes() + b'\n')
+            if bgzf:
+                # the host-built text goes up to the device and is deflated there like the device text
+                self.io.device_to_stream(self.ops.bgzf_compress(ctx, ctx.bytes_to_device(sink.getvalue())), w)
 
 
 # ---------------------------------------------------------------------- the packers with the reference's own signature
