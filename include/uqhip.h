@@ -453,7 +453,7 @@ int uq_synth_fastq(uq_ctx* ctx, const uq_synth_spec* h_spec, uint64_t first, uin
 
 /* ---- gzip input (an extension: the reference reads plain FASTQ only).  A BGZF file (what `bgzip` writes) is a chain of independent
  * gzip members, each with its compressed size in a `BC` extra subfield (BSIZE) and at most 64 KiB of output: they inflate in parallel
- * on the device.  Any other gzip is inflated on the host.
+ * on the device.  Any other gzip is inflated on the device in parallel chunks (uq_gzip_stream_*, below).
  * uq_gzip_scan: walks the RFC 1952 member headers of h_buf[0, nbytes) (FEXTRA, FNAME, FCOMMENT, FHCRC).  *h_kind:
  *   UQ_GZIP_BGZF       every member carries BSIZE (the 28-byte EOF block and other empty members included): h_members[k] for all of them,
  *                      out_offset = the 64-bit prefix sum of ISIZE, *h_total_out = the inflated size;
@@ -483,6 +483,40 @@ int uq_gzip_scan(const uint8_t* h_buf, uint64_t nbytes, uq_gzip_member* h_member
 int uq_inflate_members(uq_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, const uq_gzip_member* d_members, uint64_t nmembers,
                        uint8_t* d_out, uint64_t out_bytes, uint32_t* d_status);
 int uq_inflate_member_host(const uint8_t* h_comp, uint64_t comp_bytes, uint8_t* h_out, uint64_t isize, uint32_t crc32, uint32_t* h_status);
+
+/* ---- gzip that is not BGZF (one member, or members without BSIZE), inflated on the device in parallel chunks: the speculative scheme of
+ * rapidgzip (uq_amd/csrc/inflate_stream.h).  Chunk starts are units packed as (canonical bit position << 2) | kind,
+ * kind 0 a member header, 1 a non-final stored block (position = 8 x the byte offset of LEN), 2 a dynamic-Huffman block (its header's bit).
+ * uq_gzip_stream_begin: d_comp[0, comp_bytes) (device; the whole gzip file) cut into chunks of chunk_bytes whose starts the finder looks
+ *   for -- or, when h_starts is not NULL, the caller's nstarts starts (host memory; wrong ones cost time, never change the output; chunk 0
+ *   always starts at byte 0) -- decoded on the device in rounds until the chain of chunk ends and starts is verified.  *h_out_bytes = the
+ *   inflated size, *h_stream = a handle for uq_gzip_stream_finish.  A damaged file: *h_status = its UQ_INF_* / UQ_GZS_* code (non-zero),
+ *   *h_bad_offset = the byte offset named in uq_last_error(), *h_stream = NULL.  Synchronises the context's stream.
+ * uq_gzip_stream_finish: the output into d_out (device, >= *h_out_bytes): chunks placed, markers resolved, every member's ISIZE and CRC-32
+ *   checked.  *h_status / *h_bad_offset as above.  uq_gzip_stream_free releases the handle (and its device workspace) whatever happened.
+ * uq_gzip_stream_get_info: counts and times of the run (uq_gzip_stream_info).
+ * uq_gzip_stream_host: the same finder, chunk decoder, chain check and resolution on the CPU, serially: h_out receives the output when
+ *   capacity >= *h_out_bytes (otherwise only *h_out_bytes is set); h_info may be NULL. */
+typedef struct uq_gzip_stream uq_gzip_stream;
+typedef struct uq_gzip_stream_info {
+    uint64_t chunks;            /* chunks after the chain check */
+    uint64_t starts;            /* chunk starts decoded in the first round (chunk 0 included) */
+    uint64_t rounds;            /* decode rounds */
+    uint64_t redecoded;         /* chunk decodes after the first round (chain mismatches, slot overflows) */
+    uint64_t overflows;         /* slot overflows of verified chunks */
+    uint64_t resolve_rounds;    /* marker resolution rounds */
+    uint64_t members;
+    uint64_t out_bytes;
+    double find_ms, decode_ms, finish_ms;
+} uq_gzip_stream_info;
+int uq_gzip_stream_begin(uq_ctx* ctx, const uint8_t* d_comp, uint64_t comp_bytes, uint64_t chunk_bytes, const uint64_t* h_starts,
+                         uint64_t nstarts, uq_gzip_stream** h_stream, uint64_t* h_out_bytes, uint32_t* h_status, uint64_t* h_bad_offset);
+int uq_gzip_stream_finish(uq_gzip_stream* stream, uint8_t* d_out, uint64_t out_bytes, uint32_t* h_status, uint64_t* h_bad_offset);
+int uq_gzip_stream_get_info(const uq_gzip_stream* stream, uq_gzip_stream_info* h_info);
+int uq_gzip_stream_free(uq_gzip_stream* stream);
+int uq_gzip_stream_host(const uint8_t* h_comp, uint64_t comp_bytes, uint64_t chunk_bytes, const uint64_t* h_starts, uint64_t nstarts,
+                        uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes, uint32_t* h_status, uint64_t* h_bad_offset,
+                        uq_gzip_stream_info* h_info);
 
 /* ---- BGZF output (an extension: the reference writes plain FASTQ only).  The deflate compressor is uq_amd/csrc/deflate_core.h: one
  * dynamic-Huffman block per 65 280-byte input block (a stored block where that is smaller), so every member is at most 65 311 bytes; a

@@ -58,6 +58,12 @@ class QnameFused(C.Structure):
                 ('nreads', C.c_uint64), ('thresholds', C.c_uint64 * 24), ('counts', (C.c_uint64 * 24) * 8)]
 
 
+class GzipStreamInfo(C.Structure):
+    _fields_ = [('chunks', C.c_uint64), ('starts', C.c_uint64), ('rounds', C.c_uint64), ('redecoded', C.c_uint64),
+                ('overflows', C.c_uint64), ('resolve_rounds', C.c_uint64), ('members', C.c_uint64), ('out_bytes', C.c_uint64),
+                ('find_ms', C.c_double), ('decode_ms', C.c_double), ('finish_ms', C.c_double)]
+
+
 class GzipMember(C.Structure):
     _fields_ = [('data_offset', C.c_uint64), ('comp_bytes', C.c_uint64), ('out_offset', C.c_uint64), ('isize', C.c_uint32),
                 ('crc32', C.c_uint32)]
@@ -153,6 +159,11 @@ SIGNATURES = {
     'uq_gzip_scan': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u64), _P(_int), _P(_u64)],
     'uq_inflate_members': [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp],
     'uq_inflate_member_host': [_vp, _u64, _vp, _u64, _u32, _P(_u32)],
+    'uq_gzip_stream_begin': [_vp, _vp, _u64, _u64, _vp, _u64, _P(_vp), _P(_u64), _P(_u32), _P(_u64)],
+    'uq_gzip_stream_finish': [_vp, _vp, _u64, _P(_u32), _P(_u64)],
+    'uq_gzip_stream_get_info': [_vp, _P(GzipStreamInfo)],
+    'uq_gzip_stream_free': [_vp],
+    'uq_gzip_stream_host': [_vp, _u64, _u64, _vp, _u64, _vp, _u64, _P(_u64), _P(_u32), _P(_u64), _P(GzipStreamInfo)],
     'uq_bgzf_bound': [_u64, _P(_u64)],
     'uq_bgzf_compress': [_vp, _vp, _u64, _vp, _u64, _P(_u64), _u32],
     'uq_bgzf_compress_block_host': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32)],

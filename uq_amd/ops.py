@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -650,7 +650,8 @@ GZIP_MEMBER = np.dtype([('data_offset', '<u8'), ('comp_bytes', '<u8'), ('out_off
 INFLATE_STATUS = {1: 'deflate data runs past the end of the member', 2: 'invalid block type', 3: 'stored block length check failed',
                   4: 'invalid code lengths set', 5: 'invalid code length repeat', 6: 'invalid Huffman code', 7: 'distance too far back',
                   8: 'more output than the trailer\'s ISIZE', 9: 'less output than the trailer\'s ISIZE', 10: 'CRC-32 mismatch',
-                  11: 'too many length or distance symbols', 12: 'member larger than 64 KiB or outside the input'}
+                  11: 'too many length or distance symbols', 12: 'member larger than 64 KiB or outside the input',
+                  13: 'bytes that are not a gzip member header', 15: 'distance too far back'}
 
 
 def is_gzip(path):
@@ -701,6 +702,72 @@ def inflate_member_host(data, isize, crc32):
     call('uq_inflate_member_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), int(isize),
          int(crc32) & 0xFFFFFFFF, C.byref(st))
     return st.value, out[:int(isize)].tobytes()
+
+
+# ------------------------------------------------------------------ other gzip: chunks inflated on the device in parallel
+GZS_MEMBER, GZS_UNCOMPRESSED, GZS_DYNAMIC = 0, 1, 2
+
+
+class GzipStreamError(ValueError):
+    """A damaged gzip stream: .status (UQ_INF_* / UQ_GZS_* code), .offset (the byte offset the message names)."""
+
+    def __init__(self, message, status, offset):
+        ValueError.__init__(self, message)
+        self.status, self.offset = status, offset
+
+
+def _starts_arg(starts):
+    if starts is None:
+        return None, C.c_void_p(0), 0
+    arr = np.ascontiguousarray(np.asarray(starts, dtype=np.uint64).reshape(-1))
+    return arr, C.c_void_p(arr.ctypes.data if arr.size else 0), arr.size
+
+
+def _info_dict(info):
+    return {k: getattr(info, k) for k, _ in GzipStreamInfo._fields_}
+
+
+def gzip_stream_to_device(ctx, d_comp, chunk_bytes, starts=None):
+    """uq_gzip_stream_begin / _finish: the gzip file d_comp (a uint8 device tensor, not BGZF or BGZF, any members) inflated on the device in
+    parallel chunks of chunk_bytes compressed bytes.  starts: the caller's chunk starts instead of the finder's ((bit << 2) | kind).
+    Returns (uint8 device tensor of the output, info dict); a damaged stream raises GzipStreamError."""
+    t = ctx.torch
+    keep, sp, ns = _starts_arg(starts)
+    h, nout, st, bad = C.c_void_p(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+    n = d_comp.numel()
+    call('uq_gzip_stream_begin', ctx.h, _p(d_comp) if n else C.c_void_p(0), n, int(chunk_bytes), sp, ns, C.byref(h), C.byref(nout),
+         C.byref(st), C.byref(bad))
+    if st.value:
+        raise GzipStreamError(load().uq_last_error().decode('utf-8', 'replace'), st.value, bad.value)
+    try:
+        out = t.empty(nout.value, dtype=t.uint8, device=ctx.device)
+        call('uq_gzip_stream_finish', h, _p(out) if nout.value else C.c_void_p(0), nout.value, C.byref(st), C.byref(bad))
+        if st.value:
+            raise GzipStreamError(load().uq_last_error().decode('utf-8', 'replace'), st.value, bad.value)
+        info = GzipStreamInfo()
+        call('uq_gzip_stream_get_info', h, C.byref(info))
+    finally:
+        call('uq_gzip_stream_free', h)
+    return out, _info_dict(info)
+
+
+def gzip_stream_host(data, chunk_bytes, starts=None):
+    """uq_gzip_stream_host: the same finder, chunk decoder, chain check and resolution on the CPU.  Returns (bytes, info dict); a damaged
+    stream raises GzipStreamError."""
+    data = bytes(data)
+    src = np.frombuffer(data, dtype=np.uint8)
+    keep, sp, ns = _starts_arg(starts)
+    nout, st, bad, info = C.c_uint64(), C.c_uint32(), C.c_uint64(), GzipStreamInfo()
+    cap = 4 * len(data) + 4096
+    while True:
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        call('uq_gzip_stream_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), int(chunk_bytes), sp, ns,
+             C.c_void_p(out.ctypes.data), cap, C.byref(nout), C.byref(st), C.byref(bad), C.byref(info))
+        if st.value:
+            raise GzipStreamError(load().uq_last_error().decode('utf-8', 'replace'), st.value, bad.value)
+        if nout.value <= cap:
+            return out[:nout.value].tobytes(), _info_dict(info)
+        cap = nout.value
 
 
 # ------------------------------------------------------------------ BGZF output (an extension: members deflated on the device)

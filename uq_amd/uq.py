@@ -29,6 +29,9 @@ import time
 
 import numpy as np
 
+# compressed bytes per chunk of a gzip file that is not BGZF, inflated on the device
+GZIP_STREAM_CHUNK = 1 << 18
+
 PATTERNS = ['0.1', '1.1', '2.1', '3.1', '0.2', '1.2', '2.2', '3.2']
 
 
@@ -57,6 +60,8 @@ def build_parser():
     p.add_argument('--device', type=int, default=int(os.environ.get('LOCAL_RANK', '0')), help='GPU index (extension)')
     p.add_argument('--quiet', action='store_true', default=False, help='suppress the analysis report (extension)')
     p.add_argument('--host-qname', action='store_true', default=False, help='run the QNAME passes sequentially on the host (extension)')
+    p.add_argument('--host-inflate', action='store_true', default=False,
+                   help='inflate gzip input that is not BGZF on the host (zlib, one thread) instead of in parallel chunks on the GPU (extension)')
     p.add_argument('--exact-qname', action='store_true', default=False,
                    help='run the QNAME passes as kernels of their own (layout, then tokeniser) instead of inside the pack kernel (extension)')
     p.add_argument('--multi-pass', action='store_true', default=False,
@@ -154,7 +159,8 @@ class Session:
     def load_gzip(self, path):
         """gzip input (an extension: the reference reads plain text only), recognised by its magic bytes.  BGZF (every member carries its
         compressed size): the compressed file goes to HBM, the member headers are walked on the host, every member inflates on the device
-        into its slice of one buffer (uq_inflate_members).  Any other gzip inflates on the host (zlib), streamed to HBM.  Then load_device."""
+        into its slice of one buffer (uq_inflate_members).  Any other gzip goes to HBM compressed and inflates there in parallel chunks
+        (uq_gzip_stream_*, GZIP_STREAM_CHUNK bytes each); --host-inflate: on the host (zlib), streamed to HBM.  Then load_device."""
         ops, ctx = self.ops, self.ctx
         kind, members, total, err = ops.gzip_scan(np.memmap(path, dtype=np.uint8, mode='r'))
         if kind == ops.GZIP_MALFORMED: error('ERROR: %s is not a readable gzip file: %s' % (path, err[0]))
@@ -168,13 +174,23 @@ class Session:
                 k, st = bad
                 error('ERROR: %s: gzip member %d (deflate data at byte %d): %s' % (path, k, int(members[k]['data_offset']),
                                                                                   ops.INFLATE_STATUS.get(st, 'status %d' % st)))
-        else:
+        elif getattr(self.args, 'host_inflate', False):
             self.gzip_path = 'gzip inflated on the host'
             import zlib
             try:
                 d_buf = self.io.gzip_to_device(path)
             except (zlib.error, EOFError) as e:
                 error('ERROR: %s is not a readable gzip file: %s' % (path, e))
+        else:
+            d_comp = self.io.file_to_device(path)
+            try:
+                d_buf, info = ops.gzip_stream_to_device(ctx, d_comp, GZIP_STREAM_CHUNK)
+            except ops.GzipStreamError as e:
+                error('ERROR: %s is not a readable gzip file: %s' % (path, e))
+            finally:
+                del d_comp
+            self.gzip_stream_info = info
+            self.gzip_path = 'gzip, %d chunks inflated on the device' % info['chunks']
         if d_buf.numel() == 0: error('ERROR: empty input')
         self.load_device(d_buf)
 
