@@ -535,6 +535,19 @@ int uq_bgzf_compress(uq_ctx* ctx, const uint8_t* d_in, uint64_t nbytes, uint8_t*
 int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
                                 uint32_t* h_status);
 
+/* ---- the size of a buffer as BGZF, without writing it (an extension: what `--test --device-compressor` sizes its candidates with).
+ * For the byte string B = prefix || data, S(B) = the sum, over the consecutive 65 280-byte blocks of B, of the size of the member
+ * uq_bgzf_compress_block_host writes for the block: the length of uq_bgzf_compress's output without the EOF member.  S of nothing is 0.
+ * uq_deflate_size: h_prefix[0, prefix_bytes) (host, at most 256 bytes: a .npy header) followed by d_data[0, nbytes) (device).  One
+ * workgroup per block runs the compressor's size-only path (deflate_core.h: uq_deflate_block_size); S is ADDED to *d_total (device, 8-byte
+ * aligned), and *d_status (device) is raised to a block's status if one fails: the caller zeroes both.  One launch whatever nbytes is, over
+ * a fixed workspace from the context's scratch pool; queued on the context's stream and not synchronised, nothing is read back: calls can
+ * be queued back to back and their totals fetched together. */
+int uq_deflate_size(uq_ctx* ctx, const uint8_t* h_prefix, uint32_t prefix_bytes, const uint8_t* d_data, uint64_t nbytes, uint64_t* d_total,
+                    uint32_t* d_status);
+/* uq_deflate_size_host: the same code on the CPU over host bytes: *h_total = S(h_prefix || h_data). */
+int uq_deflate_size_host(const uint8_t* h_prefix, uint32_t prefix_bytes, const uint8_t* h_data, uint64_t nbytes, uint64_t* h_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,8 @@ SIGNATURES = {
     'uq_bgzf_bound': [_u64, _P(_u64)],
     'uq_bgzf_compress': [_vp, _vp, _u64, _vp, _u64, _P(_u64), _u32],
     'uq_bgzf_compress_block_host': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32)],
+    'uq_deflate_size': [_vp, _vp, _u32, _vp, _u64, _vp, _vp],
+    'uq_deflate_size_host': [_vp, _u32, _vp, _u64, _P(_u64)],
 }
 
 _lib = None

@@ -75,6 +75,23 @@ struct UqDeflateLds {
     uint32_t crc0, nrle, hlit, hdist, hclen, hdr_bits, member_bytes, stored;
 };
 
+// what the size-only path (uq_deflate_block_size) needs of the above: no codes, no extra bits of the run-length code, no bit offsets, no
+// staged header, no CRC
+struct UqDeflateSizeLds {
+    uint8_t in[UQ_DEF_MAX_IN + 16];
+    uint8_t len[UQ_DEF_MAX_IN];
+    union {
+        uint32_t head[1u << UQ_DEF_HASH_BITS];
+        uint16_t jmp[UQ_DEF_WIN];
+        UqDefHuffScratch h;
+    } u;
+    uint32_t lfreq[288], dfreq[32], cfreq[20];
+    uint8_t llen[288], dlen[32], clen[20];
+    uint16_t rle[320];
+    uint16_t entry[UQ_DEF_NSUB];
+    uint32_t nrle, hlit, hdist, hclen, hdr_bits, member_bytes, stored, body_bits;
+};
+
 UQ_DEF_HD uint32_t uq_def_log2(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
 
 // the length of a len[] code, and the code of a length
@@ -98,6 +115,10 @@ UQ_DEF_HD uint32_t uq_def_dsym(uint32_t D, uint32_t& ev, uint32_t& en) {
     ev = d - ((2u + (sym & 1)) << ex); en = ex;
     return sym;
 }
+
+// the extra bits of a literal/length symbol (0..285) and of a distance symbol (0..29)
+UQ_DEF_HD uint32_t uq_def_lextra(uint32_t sym) { return sym < 265 || sym == 285 ? 0u : (sym - 261) >> 2; }
+UQ_DEF_HD uint32_t uq_def_dextra(uint32_t sym) { return sym < 4 ? 0u : (sym >> 1) - 1; }
 
 // the order in which the code-length code's lengths are sent
 UQ_DEF_HD uint32_t uq_def_order(uint32_t k) { return (uint8_t)"\x10\x11\x12\x00\x08\x07\x09\x06\x0a\x05\x0b\x04\x0c\x03\x0d\x02\x0e\x01\x0f"[k]; }
@@ -201,23 +222,25 @@ UQ_DEF_HD void uq_def_codes(const uint8_t* lens, uint32_t n, uint16_t* codes) {
         codes[s] = lens[s] ? (uint16_t)uq_inf_rev(next[lens[s]]++, lens[s]) : 0;
 }
 
-// Compresses s->in[0, n) into one BGZF member: *member_bytes = its size.  Env: sync(), lds_max / lds_add / lds_xor (atomics on LDS words),
-// dist_put(p, d) / dist_get(p) (the distance workspace, n entries), word_store(w, v) / word_or(w, v) (32-bit word w of the member; the member's
-// words are zero before the call), and x2n (the CRC shift table).  The block must already be in s->in.
-template <class Env>
-UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t cap, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
-    if (n > UQ_DEF_MAX_IN) return UQ_DEF_TOO_LARGE;
-    for (uint32_t e = tid; e < 256; e += nth) s->crctab[e] = uq_crc_table_entry(e);
+// Phases 1 to 5 on s->in[0, n) (n <= UQ_DEF_MAX_IN): the member's size in s->member_bytes, stored or dynamic in s->stored, visible to all
+// threads on return.  kEmit (Lds = UqDeflateLds) also leaves what phase 6 writes the member from: the CRC, the codes, every sub-segment's
+// first bit.  Without it (Lds = UqDeflateSizeLds) the same matches, parse, histograms and code lengths are computed and nothing else: the
+// distance workspace holds distance symbols (one byte per position will do: Env::dist_put / dist_get take and give the symbol), and the
+// bits of the tokens are counted from the histograms (sum of frequency x (code length + extra bits)) instead of by a second walk.
+template <bool kEmit, class Env, class Lds>
+UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t nth) {
+    if constexpr (kEmit)
+        for (uint32_t e = tid; e < 256; e += nth) s->crctab[e] = uq_crc_table_entry(e);
     for (uint32_t e = tid; e < (1u << UQ_DEF_HASH_BITS); e += nth) s->u.head[e] = 0;
     for (uint32_t e = tid; e < 288; e += nth) s->lfreq[e] = 0;
     for (uint32_t e = tid; e < 32; e += nth) s->dfreq[e] = 0;
     for (uint32_t e = tid; e < 20; e += nth) s->cfreq[e] = 0;
     for (uint32_t e = tid; e < 16; e += nth) s->in[n + e] = 0;
-    if (tid == 0) s->crc0 = 0;
+    if constexpr (kEmit) { if (tid == 0) s->crc0 = 0; } else { if (tid == 0) s->body_bits = 0; }
     env.sync();
 
     // ---- 1. CRC-32
-    {
+    if constexpr (kEmit) {
         const uint32_t S = (n + nth - 1) / nth;
         const uint32_t lo = tid * S < n ? tid * S : n, hi = lo + S < n ? lo + S : n;
         uint32_t c = uq_crc0_bytes(s->crctab, 0, s->in + lo, hi - lo);
@@ -238,7 +261,8 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
                     while (L < lim && s->in[c + L] == s->in[p + L]) ++L;
                     if (L >= 3 && !(L == 3 && p - c > 4096)) {
                         v = uq_def_lcode(L);
-                        env.dist_put(p, p - c);
+                        if constexpr (kEmit) env.dist_put(p, p - c);
+                        else { uint32_t dv, dn; env.dist_put(p, uq_def_dsym(p - c, dv, dn)); }
                     }
                 }
             }
@@ -287,7 +311,8 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
             uint32_t ev, en;
             const uint32_t L = uq_def_mlen(v);
             env.lds_add(&s->lfreq[uq_def_lsym(L, ev, en)], 1);
-            env.lds_add(&s->dfreq[uq_def_dsym(env.dist_get(p), ev, en)], 1);
+            if constexpr (kEmit) env.lds_add(&s->dfreq[uq_def_dsym(env.dist_get(p), ev, en)], 1);
+            else env.lds_add(&s->dfreq[env.dist_get(p)], 1);
             p += L;
         }
     }
@@ -296,8 +321,10 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
     uq_def_huffman(env, s->lfreq, 286, 15, s->llen, &s->u.h, tid, nth);
     uq_def_huffman(env, s->dfreq, 30, 15, s->dlen, &s->u.h, tid, nth);
     if (tid == 0) {
-        uq_def_codes(s->llen, 286, s->lcode);
-        uq_def_codes(s->dlen, 30, s->dcode);
+        if constexpr (kEmit) {
+            uq_def_codes(s->llen, 286, s->lcode);
+            uq_def_codes(s->dlen, 30, s->dcode);
+        }
         uint32_t hlit = 286, hdist = 30;
         while (hlit > 257 && !s->llen[hlit - 1]) --hlit;
         while (hdist > 1 && !s->dlen[hdist - 1]) --hdist;
@@ -309,16 +336,18 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
             uint32_t run = 1;
             while (run < 138 && i + run < tot && (i + run < hlit ? s->llen[i + run] : s->dlen[i + run - hlit]) == l) ++run;
             if (l == 0 && run >= 3) {                                   // 17: 3..10 zeros, 18: 11..138
-                if (run <= 10) { s->rle[nr] = 17; s->rlex[nr++] = (uint8_t)(run - 3); }
-                else { s->rle[nr] = 18; s->rlex[nr++] = (uint8_t)(run - 11); }
-                i += run; prev = 0;
+                s->rle[nr] = run <= 10 ? 17 : 18;
+                if constexpr (kEmit) s->rlex[nr] = (uint8_t)(run <= 10 ? run - 3 : run - 11);
+                ++nr; i += run; prev = 0;
             } else if (l == prev && run >= 3) {                          // 16: the previous length 3..6 times more
                 const uint32_t r = run > 6 ? 6 : run;
-                s->rle[nr] = 16; s->rlex[nr++] = (uint8_t)(r - 3);
-                i += r;
+                s->rle[nr] = 16;
+                if constexpr (kEmit) s->rlex[nr] = (uint8_t)(r - 3);
+                ++nr; i += r;
             } else {
-                s->rle[nr] = (uint16_t)l; s->rlex[nr++] = 0;
-                ++i; prev = l;
+                s->rle[nr] = (uint16_t)l;
+                if constexpr (kEmit) s->rlex[nr] = 0;
+                ++nr; ++i; prev = l;
             }
         }
         for (uint32_t k = 0; k < nr; ++k) s->cfreq[s->rle[k]]++;
@@ -327,7 +356,7 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
     env.sync();
     uq_def_huffman(env, s->cfreq, 19, 7, s->clen, &s->u.h, tid, nth);
     if (tid == 0) {
-        uq_def_codes(s->clen, 19, s->ccode);
+        if constexpr (kEmit) uq_def_codes(s->clen, 19, s->ccode);
         uint32_t hclen = 19;
         while (hclen > 4 && !s->clen[uq_def_order(hclen - 1)]) --hclen;
         uint32_t b = 3 + 5 + 5 + 4 + 3 * hclen;
@@ -340,30 +369,65 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
     env.sync();
 
     // ---- 5. bits of every sub-segment, the member's size, stored or not
-    for (uint32_t k = tid; k < nsub; k += nth) {
-        const uint32_t end = (k + 1) * UQ_DEF_SUB < n ? (k + 1) * UQ_DEF_SUB : n;
-        uint32_t b = 0;
-        for (uint32_t p = s->entry[k]; p < end;) {
-            const uint32_t v = s->len[p];
-            if (!v) { b += s->llen[s->in[p]]; ++p; continue; }
-            uint32_t ev, en, dv, dn;
-            const uint32_t L = uq_def_mlen(v);
-            const uint32_t ls = uq_def_lsym(L, ev, en), ds = uq_def_dsym(env.dist_get(p), dv, dn);
-            b += s->llen[ls] + en + s->dlen[ds] + dn;
-            p += L;
+    if constexpr (kEmit) {
+        for (uint32_t k = tid; k < nsub; k += nth) {
+            const uint32_t end = (k + 1) * UQ_DEF_SUB < n ? (k + 1) * UQ_DEF_SUB : n;
+            uint32_t b = 0;
+            for (uint32_t p = s->entry[k]; p < end;) {
+                const uint32_t v = s->len[p];
+                if (!v) { b += s->llen[s->in[p]]; ++p; continue; }
+                uint32_t ev, en, dv, dn;
+                const uint32_t L = uq_def_mlen(v);
+                const uint32_t ls = uq_def_lsym(L, ev, en), ds = uq_def_dsym(env.dist_get(p), dv, dn);
+                b += s->llen[ls] + en + s->dlen[ds] + dn;
+                p += L;
+            }
+            s->bits[k] = b;
         }
-        s->bits[k] = b;
+        env.sync();
+        if (tid == 0) {
+            uint32_t off = 144 + s->hdr_bits;
+            for (uint32_t k = 0; k < nsub; ++k) { const uint32_t b = s->bits[k]; s->bits[k] = off; off += b; }
+            s->bits[nsub] = off;                                            // end-of-block code, padding, trailer
+            const uint32_t dyn = 18 + (off + s->llen[256] - 144 + 7) / 8 + 8, stored = 18 + 5 + n + 8;
+            s->stored = stored <= dyn;
+            s->member_bytes = s->stored ? stored : dyn;
+        }
+        env.sync();
+    } else {
+        // a token's bits are its symbols' code lengths and extra bits; lfreq[256] = 1 stands for the end-of-block code
+        uint32_t b = 0;
+        for (uint32_t e = tid; e < 286; e += nth) b += s->lfreq[e] * (s->llen[e] + uq_def_lextra(e));
+        for (uint32_t e = tid; e < 30; e += nth) b += s->dfreq[e] * (s->dlen[e] + uq_def_dextra(e));
+        if (b) env.lds_add(&s->body_bits, b);
+        env.sync();
+        if (tid == 0) {
+            const uint32_t dyn = 18 + (s->hdr_bits + s->body_bits + 7) / 8 + 8, stored = 18 + 5 + n + 8;
+            s->stored = stored <= dyn;
+            s->member_bytes = s->stored ? stored : dyn;
+        }
+        env.sync();
     }
-    env.sync();
-    if (tid == 0) {
-        uint32_t off = 144 + s->hdr_bits;
-        for (uint32_t k = 0; k < nsub; ++k) { const uint32_t b = s->bits[k]; s->bits[k] = off; off += b; }
-        s->bits[nsub] = off;                                            // end-of-block code, padding, trailer
-        const uint32_t dyn = 18 + (off + s->llen[256] - 144 + 7) / 8 + 8, stored = 18 + 5 + n + 8;
-        s->stored = stored <= dyn;
-        s->member_bytes = s->stored ? stored : dyn;
-    }
-    env.sync();
+}
+
+// The size of the BGZF member that uq_deflate_block writes for s->in[0, n), and nothing written.  Env: sync(), lds_max / lds_add, and
+// dist_put(p, sym) / dist_get(p) (one distance symbol, 0..29, per position: n entries).  The block must already be in s->in.
+template <class Env>
+UQ_DEF_HD int uq_deflate_block_size(Env& env, UqDeflateSizeLds* s, uint32_t n, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+    if (n > UQ_DEF_MAX_IN) return UQ_DEF_TOO_LARGE;
+    uq_def_plan<false>(env, s, n, tid, nth);
+    *member_bytes = s->member_bytes;
+    return UQ_DEF_OK;
+}
+
+// Compresses s->in[0, n) into one BGZF member: *member_bytes = its size.  Env: sync(), lds_max / lds_add / lds_xor (atomics on LDS words),
+// dist_put(p, d) / dist_get(p) (the distance workspace, n entries), word_store(w, v) / word_or(w, v) (32-bit word w of the member; the member's
+// words are zero before the call), and x2n (the CRC shift table).  The block must already be in s->in.
+template <class Env>
+UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t cap, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+    if (n > UQ_DEF_MAX_IN) return UQ_DEF_TOO_LARGE;
+    uq_def_plan<true>(env, s, n, tid, nth);
+    const uint32_t nsub = (n + UQ_DEF_SUB - 1) / UQ_DEF_SUB;
     const uint32_t mb = s->member_bytes;
     *member_bytes = mb;
     if (mb > cap) return UQ_DEF_NO_SPACE;

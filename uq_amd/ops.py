@@ -808,3 +808,47 @@ def bgzf_block_host(data, capacity=None):
     if st.value:
         raise ValueError('bgzf_block_host: %s' % DEFLATE_STATUS.get(st.value, 'status %d' % st.value))
     return out[:nout.value].tobytes()
+
+
+# ------------------------------------------------------------------ the size of a buffer as BGZF (the --test sizer)
+def deflate_size_host(data, prefix=b''):
+    """uq_deflate_size_host: S(prefix + data) on the CPU -- the bytes ops.bgzf_compress(prefix + data, eof=False) would have."""
+    data, prefix = bytes(data), bytes(prefix)
+    src = np.frombuffer(data, dtype=np.uint8)
+    pre = np.frombuffer(prefix, dtype=np.uint8)
+    out = C.c_uint64()
+    call('uq_deflate_size_host', C.c_void_p(pre.ctypes.data if pre.size else 0), len(prefix), C.c_void_p(src.ctypes.data if src.size else 0),
+         len(data), C.byref(out))
+    return out.value
+
+
+class DeflateSizes:
+    """uq_deflate_size for up to `capacity` buffers: add() queues one (nothing is read back, the stream is not synchronised), fetch()
+    reads all the totals back at once.  A buffer passed to add() may be overwritten by work queued behind it on the context's stream."""
+
+    def __init__(self, ctx, capacity):
+        self.ctx, self.capacity, self.n = ctx, int(capacity), 0
+        self.slots = ctx.torch.zeros(2 * self.capacity, dtype=ctx.torch.int64, device=ctx.device)      # totals, then one status each
+
+    def add(self, prefix, d_data):
+        """Queues S(prefix + the bytes of the device tensor d_data); returns its index in fetch()'s list."""
+        if self.n >= self.capacity: raise ValueError('DeflateSizes: more than %d buffers' % self.capacity)
+        prefix = bytes(prefix)
+        nbytes = d_data.numel() * d_data.element_size()
+        call('uq_deflate_size', self.ctx.h, prefix, len(prefix), _p(d_data) if nbytes else C.c_void_p(0), nbytes,
+             _p(self.slots[self.n:]), _p(self.slots[self.capacity + self.n:]))
+        self.n += 1
+        return self.n - 1
+
+    def fetch(self):
+        host = self.ctx.to_numpy(self.slots)
+        bad = [k for k in range(self.n) if host[self.capacity + k]]
+        if bad: raise ValueError('deflate_size: buffer %d: %s' % (bad[0], DEFLATE_STATUS.get(int(host[self.capacity + bad[0]]), 'failed')))
+        return [int(v) for v in host[:self.n]]
+
+
+def deflate_size(ctx, prefix, d_data):
+    """S(prefix + the bytes of d_data) for one buffer (queue, then read back)."""
+    q = DeflateSizes(ctx, 1)
+    q.add(prefix, d_data)
+    return q.fetch()[0]

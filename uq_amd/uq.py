@@ -2,7 +2,7 @@
 """uq -- FASTQ <-> uQ (tar of .npy arrays + config.json) on MI355X.  Drop-in for the reference script:
 
     python -m uq_amd.uq -i reads.fastq [--sort DNA|QUAL|QNAME|None] [--raw DNA QUAL QNAME] [--pattern a b]
-                        [--notricks] [--pad] [--peek] [--test [--compressor CMD]] [-o out.uQ] [--temp DIR]
+                        [--notricks] [--pad] [--peek] [--test [--compressor CMD | --device-compressor]] [-o out.uQ] [--temp DIR]
     python -m uq_amd.uq -i reads.fastq.uQ --decode > reads.fastq
 
 Same thirteen flags and validation as uq.py:21-71, same container (uq.py:897-913), same function names
@@ -71,6 +71,9 @@ def build_parser():
                    help='decode through the fixed-pitch text arrays (uq_unpack + uq_emit_fastq) instead of the fused kernel (extension)')
     p.add_argument('--bgzf', action='store_true', default=False,
                    help='with --decode: write BGZF-compressed FASTQ (what bgzip writes), deflated on the GPU (extension)')
+    p.add_argument('--device-compressor', action='store_true', default=False,
+                   help='with --test: size every candidate on the GPU with the built-in deflate sizer (its size as BGZF from this '
+                        "project's own compressor) instead of piping it through --compressor (extension)")
     return p
 
 
@@ -88,6 +91,9 @@ def validate_args(args):
         if 'none' in args.raw:
             args.raw.add(None); args.raw.discard('none')
     if getattr(args, 'bgzf', False) and not args.decode: error('ERROR: --bgzf compresses decoded FASTQ: use it together with --decode')
+    if getattr(args, 'device_compressor', False):
+        if args.compressor: error('ERROR: --device-compressor and --compressor are two ways to size the same candidates: give one of them')
+        if not args.test: error('ERROR: --device-compressor sizes the candidates of --test: use it together with --test')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     return args
 
@@ -476,8 +482,22 @@ class Session:
         if not isinstance(payload, np.ndarray): payload = self.ctx.to_numpy(payload)
         return header + payload.tobytes()
 
-    def compressed_size(self, data):
-        """uq.py:277-285 (Q4/Q26 fixed: spawn on demand, serialise first, surface errors)."""
+    @property
+    def device_sizer(self):
+        return bool(getattr(self.args, 'device_compressor', False))
+
+    @property
+    def has_compressor(self):
+        """--compressor CMD or --device-compressor: the candidates of --test are sized by something."""
+        return self.args.compressor is not None or self.device_sizer
+
+    def compressed_size(self, data, tensor=None):
+        """uq.py:277-285 (Q4/Q26 fixed: spawn on demand, serialise first, surface errors).  The device form, compressed_size(header,
+        tensor): the member is the .npy header `data` followed by the bytes of a device tensor, which stay where they are -- with
+        --device-compressor its size as BGZF (uq_deflate_size), otherwise the member goes to the host and through the command."""
+        if tensor is not None:
+            if self.device_sizer: return self.ops.deflate_size(self.ctx, data, tensor)
+            data = data + self.ctx.to_numpy(tensor).tobytes()
         if not self.args.compressor: return len(data)
         p = subprocess.run(self.args.compressor + ' | wc -c', shell=True, input=data, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
         if p.returncode != 0: error('ERROR: the compressor command failed')
@@ -488,12 +508,21 @@ class Session:
         """uq.py:290-334: size of each candidate layout -> [size, pattern] of the smallest."""
         args = self.args
         t, rows, cols = table
-        if args.compressor is None: return [rows * cols, '0.1']
+        if not self.has_compressor: return [rows * cols, '0.1']
         if filename.startswith('DNA'): pattern = None if args.pattern is None else args.pattern[0]
         elif filename.startswith('QUAL'): pattern = None if args.pattern is None else args.pattern[1]
         else: error('ERROR: This should never happen!')
         results = []
-        for pat in (PATTERNS if pattern is None else [pattern]):
+        pats = PATTERNS if pattern is None else [pattern]
+        if self.device_sizer:
+            # every layout into the one table-sized buffer and sized there, queued back to back; the totals come back together
+            sizes = self.ops.DeflateSizes(self.ctx, len(pats))
+            payload = self.ctx.empty(rows * cols)
+            for pat in pats:
+                self.ops.pattern(self.ctx, t, rows, cols, pat, out=payload)
+                sizes.add(pattern_header(rows, cols, pat), payload)
+            return sorted([size, pat] for size, pat in zip(sizes.fetch(), pats))[0]
+        for pat in pats:
             payload = self.ops.pattern(self.ctx, t, rows, cols, pat)
             blob = pattern_header(rows, cols, pat) + self.ctx.to_numpy(payload).tobytes()
             results.append([self.compressed_size(blob), pat])
@@ -528,9 +557,7 @@ class Session:
                 k = ops.narrow(ctx, skey, isz)
             else:
                 k = ops.narrow(ctx, ops.gather_rows(ctx, key.view(ctx.torch.uint8), rows, 4, sort_order).view(ctx.torch.int32), isz)
-            if test:
-                k_host = ctx.to_numpy(k, self._npdtype(isz))
-                test[out_name] = self.compressed_size(npy_header(k_host.shape, False, k_host.dtype) + k_host.tobytes())
+            if test: test[out_name] = self.compressed_size(npy_header((k.numel(),), False, self._npdtype(isz)), k)
             else: self.write_out(k, out_name, self._npdtype(isz))
             table = (uniq, nu, cols)
             if test: test[table_name] = self.test_patterns(table, table_name)
@@ -546,9 +573,7 @@ class Session:
         ncols = len(cols_d)
 
         def emit(name, tensor, dtype):
-            if test:
-                host = ctx.to_numpy(tensor, np.dtype(dtype))
-                test[name] = self.compressed_size(npy_header(host.shape, False, host.dtype) + host.tobytes())
+            if test: test[name] = self.compressed_size(npy_header((tensor.numel(),), False, np.dtype(dtype)), tensor)
             else: self.write_out(tensor, name, np.dtype(dtype))
 
         if raw:
@@ -611,7 +636,7 @@ class Session:
         self.split_time()
         raw_grid = [('DNA', 'QUAL', 'QNAME'), ('DNA', 'QUAL'), ('QUAL', 'QNAME'), ('DNA', 'QNAME'), ('DNA',), ('QUAL',), ('QNAME',), (None,)]
         for raw_tables in (raw_grid if args.raw is None else [args.raw]):
-            if args.compressor is None: args.sort = (None,)
+            if not self.has_compressor: args.sort = (None,)
             for to_sort in (['DNA', 'QUAL', 'QNAME', None] if args.sort is None else [args.sort]):
                 all_results.append(self.run_mix(to_sort, raw_tables, True))
                 say(self.split_time().ljust(27), str(to_sort).ljust(10), str(tuple(raw_tables)).ljust(32), 'All' if args.raw is None else str(args.pattern))
@@ -621,7 +646,7 @@ class Session:
         args.pattern = (best['DNA.raw'][1] if 'DNA.raw' in best else best['DNA'][1],
                         best['QUAL.raw'][1] if 'QUAL.raw' in best else best['QUAL'][1])
         say('\nAll done!')
-        say('Size (compressed)    Sort:    Raw Tables:                 Raw stats:' if args.compressor else
+        say('Size (compressed)    Sort:    Raw Tables:                 Raw stats:' if self.has_compressor else
             '             Size    Sort:    Raw Tables:                 Raw stats:')
         for result in sorted(all_results, key=lambda k: k['total_size']):
             rest = {k: v for k, v in result.items() if k not in ('total_size', 'sorted_on', 'raw_tables')}
