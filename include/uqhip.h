@@ -530,6 +530,24 @@ int uq_bgzf_bound(uint64_t nbytes, uint64_t* h_bound);
 #define UQ_BGZF_EOF 1u
 int uq_bgzf_compress(uq_ctx* ctx, const uint8_t* d_in, uint64_t nbytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* h_out_bytes,
                      uint32_t flags);
+/* uq_bgzf_compress_parts: several buffers as one run of BGZF members (what the `--gz` container writer calls once for all tar members).
+ * Part k is h_prefix[0, prefix_bytes) (host, at most 256 bytes: a .npy header) followed by d_data[0, nbytes) (device, any alignment); the
+ * 65 280-byte block cuts restart at every part, so part k's members are exactly uq_bgzf_compress(prefix || data) without the EOF member
+ * and h_part_bytes[k] (host) = S(prefix || data) of uq_deflate_size.  One block table for all parts is built on the host and uploaded
+ * once; the chunks of blocks run across the parts.  The members of all parts follow each other in d_out; *h_out_bytes = their total (plus
+ * the EOF member with UQ_BGZF_EOF).  A block that fails is an error naming the part and the block; a capacity that is too small is an
+ * error and nothing is written past it.  Synchronises the context's stream.
+ * uq_bgzf_parts_bound: *h_bound = the capacity uq_bgzf_compress_parts needs (EOF member included). */
+typedef struct uq_bgzf_part {
+    const uint8_t* h_prefix;    /* host */
+    uint32_t prefix_bytes;      /* <= 256 */
+    uint32_t reserved;
+    const uint8_t* d_data;      /* device */
+    uint64_t nbytes;
+} uq_bgzf_part;
+int uq_bgzf_compress_parts(uq_ctx* ctx, const uq_bgzf_part* h_parts, uint32_t nparts, uint8_t* d_out, uint64_t out_capacity,
+                           uint64_t* h_part_bytes, uint64_t* h_out_bytes, uint32_t flags);
+int uq_bgzf_parts_bound(const uq_bgzf_part* h_parts, uint32_t nparts, uint64_t* h_bound);
 /* uq_bgzf_compress_block_host: the same compressor on the CPU, on one block (nbytes <= 65 280): h_out[0, capacity) receives the member,
  * *h_out_bytes = its size.  *h_status = 0, 1 (the member needs more than `capacity` bytes: nothing but zeros written) or 2 (nbytes too large). */
 int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,

@@ -69,6 +69,11 @@ class GzipMember(C.Structure):
                 ('crc32', C.c_uint32)]
 
 
+class BgzfPart(C.Structure):
+    _fields_ = [('h_prefix', C.c_void_p), ('prefix_bytes', C.c_uint32), ('reserved', C.c_uint32), ('d_data', C.c_void_p),
+                ('nbytes', C.c_uint64)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -166,6 +171,8 @@ SIGNATURES = {
     'uq_gzip_stream_host': [_vp, _u64, _u64, _vp, _u64, _vp, _u64, _P(_u64), _P(_u32), _P(_u64), _P(GzipStreamInfo)],
     'uq_bgzf_bound': [_u64, _P(_u64)],
     'uq_bgzf_compress': [_vp, _vp, _u64, _vp, _u64, _P(_u64), _u32],
+    'uq_bgzf_compress_parts': [_vp, _P(BgzfPart), _u32, _vp, _u64, _P(_u64), _P(_u64), _u32],
+    'uq_bgzf_parts_bound': [_P(BgzfPart), _u32, _P(_u64)],
     'uq_bgzf_compress_block_host': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32)],
     'uq_deflate_size': [_vp, _vp, _u32, _vp, _u64, _vp, _vp],
     'uq_deflate_size_host': [_vp, _u32, _vp, _u64, _P(_u64)],

@@ -399,6 +399,10 @@ class ShardedSession(Session):
                 text = self.ops.bgzf_compress(self.ctx, text, eof=self.rank == self.world - 1)
             return text, lo, n
         text, lo, n = self.guarded(my_text, 'decoding ' + str(self.args.input))
+        if os.environ.get('UQ_TIMING') and self.inflated_members is not None:
+            # a BGZF container: what this rank inflated, next to what the file holds
+            print(json.dumps({'uq_container': 'bgzf', 'rank': self.rank, 'members': len(self.source.members),
+                              'inflated_members': self.inflated_members}), file=sys.stderr, flush=True)
         shard = uqdist.Shard(self.be, lo, n, self.group)
         sizes = shard.gather_ints(int(text.numel()))
         offset, total = sum(sizes[:self.rank]), sum(sizes)
@@ -429,9 +433,7 @@ class ShardedSession(Session):
         """Rows of a 2-D member / elements of a 1-D one, from its .npy header."""
         import io as _io
         offset, size = members[name]
-        with open(self.tar_path, 'rb') as fh:
-            fh.seek(offset)
-            f = _io.BytesIO(fh.read(min(size, 65536)))
+        f = _io.BytesIO(self.source.read_host(offset, min(size, 65536)))
         version = np.lib.format.read_magic(f)
         shape, _, _ = np.lib.format.read_array_header_1_0(f) if version == (1, 0) else np.lib.format.read_array_header_2_0(f)
         if len(shape) == 1: return int(shape[0])
@@ -445,6 +447,21 @@ def main(argv=None):
         if is_gzip(args.input):
             # before any device or process-group set-up: every rank reads the same two bytes and stops alike
             print('ERROR: the sharded encoder reads plain FASTQ only; encode gzip input on one GPU (python -m uq_amd.uq) or decompress it first')
+            return 1
+    if getattr(args, 'gz', False) and not args.decode:
+        print('ERROR: the sharded encoder writes a plain .uQ only; --gz is for the single-GPU encoder (python -m uq_amd.uq)')
+        return 1
+    if args.decode and args.input and os.path.isfile(args.input):
+        # the same before any set-up: a gzip container that is not BGZF has no random access, every rank would inflate all of it
+        from . import container, ops
+        try:
+            if container.sniff(args.input) == container.GZIP:
+                if ops.gzip_scan(np.memmap(args.input, dtype=np.uint8, mode='r'))[0] == ops.GZIP_OTHER:
+                    print('ERROR: the sharded decoder reads plain and BGZF containers only; decode this gzip container on one GPU '
+                          '(python -m uq_amd.uq --decode) or recompress it with bgzip')
+                    return 1
+        except UqError as e:
+            print(e)
             return 1
     import torch
     import torch.distributed as dist

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -772,6 +772,7 @@ def gzip_stream_host(data, chunk_bytes, starts=None):
 
 # ------------------------------------------------------------------ BGZF output (an extension: members deflated on the device)
 BGZF_BLOCK = 65280
+BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
 DEFLATE_STATUS = {1: 'the member needs more than the output capacity', 2: 'more than 65 280 input bytes'}
 
 
@@ -791,6 +792,56 @@ def bgzf_compress(ctx, d_text, eof=True):
     nout = C.c_uint64()
     call('uq_bgzf_compress', ctx.h, _p(d_text) if n else C.c_void_p(0), n, _p(out), out.numel(), C.byref(nout), 1 if eof else 0)
     return out[:nout.value]
+
+
+def _bgzf_parts_arg(parts):
+    """[(prefix bytes, uint8 device tensor or None)] -> (the uq_bgzf_part array, what must stay alive while it is used)."""
+    arr = (BgzfPart * max(len(parts), 1))()
+    keep = []
+    for k, (prefix, d_data) in enumerate(parts):
+        prefix = bytes(prefix)
+        pre = np.frombuffer(prefix, dtype=np.uint8)
+        nbytes = 0 if d_data is None else d_data.numel() * d_data.element_size()
+        keep.append((pre, d_data))
+        arr[k].h_prefix = pre.ctypes.data if pre.size else None
+        arr[k].prefix_bytes = len(prefix)
+        arr[k].d_data = d_data.data_ptr() if nbytes else None
+        arr[k].nbytes = nbytes
+    return arr, keep
+
+
+def bgzf_parts_bound(parts):
+    """uq_bgzf_parts_bound: the output capacity bgzf_compress_parts needs."""
+    arr, keep = _bgzf_parts_arg(parts)
+    out = C.c_uint64()
+    call('uq_bgzf_parts_bound', arr, len(parts), C.byref(out))
+    return out.value
+
+
+def bgzf_compress_parts(ctx, parts, eof=False, capacity=None):
+    """uq_bgzf_compress_parts: parts = [(prefix bytes (<= 256), device tensor)]; every part's prefix + data as BGZF members, the block cuts
+    restarting at each part, all parts compressed in one run.  Returns (uint8 device tensor of the members of all parts in order, [bytes
+    of each part]).  `capacity`: the output buffer's size instead of bgzf_parts_bound's."""
+    t = ctx.torch
+    arr, keep = _bgzf_parts_arg(parts)
+    cap = bgzf_parts_bound(parts) if capacity is None else int(capacity)
+    out = t.empty(cap, dtype=t.uint8, device=ctx.device)
+    sizes = (C.c_uint64 * max(len(parts), 1))()
+    nout = C.c_uint64()
+    call('uq_bgzf_compress_parts', ctx.h, arr, len(parts), _p(out) if cap else C.c_void_p(0), cap, sizes, C.byref(nout), 1 if eof else 0)
+    return out[:nout.value], [int(sizes[k]) for k in range(len(parts))]
+
+
+def bgzf_compress_parts_host(parts, eof=False):
+    """The host twin of bgzf_compress_parts over host bytes: parts = [(prefix bytes, data bytes)].  Returns (bytes, [bytes of each part])."""
+    out, sizes = [], []
+    for prefix, data in parts:
+        whole = bytes(prefix) + bytes(data)
+        members = [bgzf_block_host(whole[o:o + BGZF_BLOCK]) for o in range(0, len(whole), BGZF_BLOCK)]
+        sizes.append(sum(len(m) for m in members))
+        out.extend(members)
+    if eof: out.append(BGZF_EOF)
+    return b''.join(out), sizes
 
 
 def bgzf_block_host(data, capacity=None):

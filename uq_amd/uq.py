@@ -71,6 +71,9 @@ def build_parser():
                    help='decode through the fixed-pitch text arrays (uq_unpack + uq_emit_fastq) instead of the fused kernel (extension)')
     p.add_argument('--bgzf', action='store_true', default=False,
                    help='with --decode: write BGZF-compressed FASTQ (what bgzip writes), deflated on the GPU (extension)')
+    p.add_argument('--gz', action='store_true', default=False,
+                   help='write the container BGZF-compressed (reads.fastq.uQ.gz), its tables deflated on the GPU; --decode reads such a file, and '
+                        'any gzip of a .uQ, by its content (extension)')
     p.add_argument('--device-compressor', action='store_true', default=False,
                    help='with --test: size every candidate on the GPU with the built-in deflate sizer (its size as BGZF from this '
                         "project's own compressor) instead of piping it through --compressor (extension)")
@@ -91,6 +94,9 @@ def validate_args(args):
         if 'none' in args.raw:
             args.raw.add(None); args.raw.discard('none')
     if getattr(args, 'bgzf', False) and not args.decode: error('ERROR: --bgzf compresses decoded FASTQ: use it together with --decode')
+    if getattr(args, 'gz', False):
+        if args.decode: error('ERROR: --gz compresses the container the encoder writes: --decode recognises a compressed container by itself')
+        if args.peek: error('ERROR: --gz compresses the container the encoder writes: --peek writes none')
     if getattr(args, 'device_compressor', False):
         if args.compressor: error('ERROR: --device-compressor and --compressor are two ways to size the same candidates: give one of them')
         if not args.test: error('ERROR: --device-compressor sizes the candidates of --test: use it together with --test')
@@ -133,6 +139,11 @@ class Session:
         self.t0 = time.time()
         self.split = self.t0
         self.last_subprocess_used = 0
+        self.tar_mtime = None      # the mtime of the tar headers write_container writes (None: now)
+        self.gz_bytes = None       # --gz: the bytes of the file written
+        self.gz_layout = None      # --gz: name -> {'frame': (offset, bytes), 'data': (offset, bytes)} in the compressed file
+        self.tar_path = None
+        self.source = None         # decode: the container's byte source (uq_amd/container.py)
 
     def say(self, *a):
         if not getattr(self.args, 'quiet', False):
@@ -684,38 +695,76 @@ class Session:
             done = 0
             while done < len(mv): done += os.pwrite(fd, mv[done:], pos + done)
 
+        entries = [('config.json', (blob, np.zeros(0, np.uint8)))] + [(k, self.members[k]) for k in sorted(self.members, key=order)]
+        mtime = int(time.time()) if self.tar_mtime is None else int(self.tar_mtime)
         try:
             tmp = os.path.join(tmpdir, 'temp.uq')
             # The tar stream tarfile.open(mode='w').addfile() would write (header block, data, padding to 512,
             # two zero blocks, padding to RECORDSIZE), with the payloads streamed HBM -> pinned -> pwrite.
             fd = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             try:
-                pos = 0
-                for name, (header, payload) in [('config.json', (blob, np.zeros(0, np.uint8)))] + [(k, self.members[k]) for k in sorted(self.members, key=order)]:
-                    nbytes = payload.nbytes if isinstance(payload, np.ndarray) else payload.numel() * payload.element_size()
-                    ti = tarfile.TarInfo(name); ti.size = len(header) + nbytes; ti.mtime = int(time.time())
-                    head = ti.tobuf(tarfile.DEFAULT_FORMAT, tarfile.ENCODING, 'surrogateescape') + header
-                    pwrite_all(fd, head, pos); pos += len(head)
-                    if isinstance(payload, np.ndarray):
-                        if nbytes: pwrite_all(fd, np.ascontiguousarray(payload), pos)
-                    else:
-                        self.io.device_to_fd(payload, fd, pos)
-                    pos += nbytes
-                    pad = -ti.size % tarfile.BLOCKSIZE
-                    if pad: pwrite_all(fd, b'\0' * pad, pos); pos += pad
-                end = 2 * tarfile.BLOCKSIZE
-                end += -(pos + end) % tarfile.RECORDSIZE
-                pwrite_all(fd, b'\0' * end, pos)
+                if getattr(args, 'gz', False): self.write_gz(fd, entries, mtime, pwrite_all)
+                else: self.write_plain(fd, entries, mtime, pwrite_all)
             finally:
                 os.close(fd)
             shutil.move(tmp, path)
         finally:
             shutil.rmtree(tmpdir, ignore_errors=True)
 
+    def write_plain(self, fd, entries, mtime, pwrite_all):
+        pos = 0
+        for name, (header, payload) in entries:
+            nbytes = payload.nbytes if isinstance(payload, np.ndarray) else payload.numel() * payload.element_size()
+            ti = tarfile.TarInfo(name); ti.size = len(header) + nbytes; ti.mtime = mtime
+            head = ti.tobuf(tarfile.DEFAULT_FORMAT, tarfile.ENCODING, 'surrogateescape') + header
+            pwrite_all(fd, head, pos); pos += len(head)
+            if isinstance(payload, np.ndarray):
+                if nbytes: pwrite_all(fd, np.ascontiguousarray(payload), pos)
+            else:
+                self.io.device_to_fd(payload, fd, pos)
+            pos += nbytes
+            pad = -ti.size % tarfile.BLOCKSIZE
+            if pad: pwrite_all(fd, b'\0' * pad, pos); pos += pad
+        end = 2 * tarfile.BLOCKSIZE
+        end += -(pos + end) % tarfile.RECORDSIZE
+        pwrite_all(fd, b'\0' * end, pos)
+
+    def write_gz(self, fd, entries, mtime, pwrite_all):
+        """--gz: the same tar as member-aligned BGZF.  Every member's .npy header + payload is one data part, cut
+        into 65 280-byte blocks from its own start and deflated on the device, all parts in one uq_bgzf_compress_parts call; the tar
+        framing between the parts (padding + the next header; at the end the closing zeros) is one small member each, compressed on
+        the host by the same code.  So a part's bytes in the file are exactly what --test --device-compressor reports for it."""
+        from . import container
+        ops, ctx = self.ops, self.ctx
+        parts, sizes = [], []
+        for name, (header, payload) in entries:
+            if isinstance(payload, np.ndarray):                # host payloads (config.json's is empty) go up as they are
+                payload = ctx.to_device(np.ascontiguousarray(payload).reshape(-1).view(np.uint8)) if payload.nbytes else None
+            if len(header) > 256:                              # config.json: all "header", no payload -- it is the part's data
+                if payload is not None: error('ERROR: member %s has a header of %d bytes; --gz takes .npy headers of at most 256' % (name, len(header)))
+                header, payload = b'', ctx.bytes_to_device(header)
+            parts.append((header, payload))
+            sizes.append(len(header) + (0 if payload is None else payload.numel() * payload.element_size()))
+        frames = [ops.bgzf_block_host(f) for f in container.framing_pieces([(e[0], n) for e, n in zip(entries, sizes)], mtime)]
+        d_out, part_bytes = ops.bgzf_compress_parts(ctx, parts)
+        layout = container.member_aligned_layout([len(f) for f in frames], part_bytes)
+        src = 0
+        for k, entry in enumerate(layout):
+            pwrite_all(fd, frames[k], entry['frame'][0])
+            if entry['data'] is not None:
+                o, n = entry['data']
+                if n: self.io.device_to_fd(d_out[src:src + n], fd, o)
+                src += n
+        end = layout[-1]['frame'][0] + layout[-1]['frame'][1]
+        pwrite_all(fd, ops.BGZF_EOF, end)
+        self.gz_layout = {e[0]: lay for e, lay in zip(entries, layout)}
+        self.gz_layout[None] = layout[-1]
+        self.gz_bytes = end + len(ops.BGZF_EOF)
+
     # ------------------------------------------------------------------ whole encode
     def encode(self):
         args = self.args
-        if args.output is None: args.output = args.input + '.uQ'
+        if args.output is None: args.output = args.input + ('.uQ.gz' if getattr(args, 'gz', False) else '.uQ')
         self.say('Warming up...')
         self.load(args.input)
         self.encode_loaded()
@@ -749,9 +798,7 @@ class Session:
         `rows` = (lo, hi): only that range of rows / elements (the sharded decoder; a row-major payload is read
         as a slice of the file, any other layout whole)."""
         offset, size = members[file_name]
-        with open(self.tar_path, 'rb') as fh:
-            fh.seek(offset)
-            f = io.BytesIO(fh.read(min(size, 65536)))
+        f = io.BytesIO(self.source.read_host(offset, min(size, 65536)))
         version = np.lib.format.read_magic(f)
         shape, fortran, dtype = np.lib.format.read_array_header_1_0(f) if version == (1, 0) else np.lib.format.read_array_header_2_0(f)
         hdr = f.tell()
@@ -765,14 +812,14 @@ class Session:
             tt = self.ctx.torch
             isz = np.dtype(dtype).itemsize
             lo, hi = rows if rows is not None else (0, shape[0])
-            d_pay = self.io.file_to_device(self.tar_path, offset + hdr + lo * isz, (hi - lo) * isz)
+            d_pay = self.source.to_device(offset + hdr + lo * isz, (hi - lo) * isz)
             return d_pay.view({1: tt.uint8, 2: tt.int16, 4: tt.int32, 8: tt.int64}[isz])
         k = int(pattern[0])
         nrows, cols = (shape if k % 2 == 0 else shape[::-1])
         if rows is not None and pattern == '0.1':
             lo, hi = rows
-            return (self.io.file_to_device(self.tar_path, offset + hdr + lo * cols, (hi - lo) * cols), hi - lo, cols)
-        d_pay = self.io.file_to_device(self.tar_path, offset + hdr, size - hdr)
+            return (self.source.to_device(offset + hdr + lo * cols, (hi - lo) * cols), hi - lo, cols)
+        d_pay = self.source.to_device(offset + hdr, size - hdr)
         # numpy flags 1-wide arrays as C order whatever the pattern asked for: the byte stream is the same
         t = d_pay if pattern == '0.1' else self.ops.unpattern(self.ctx, d_pay, nrows, cols, pattern)   # 0.1 is the table itself
         if rows is not None:
@@ -791,15 +838,26 @@ class Session:
 
     def open_container(self):
         """Tar members (name -> (payload offset, size)) and config.json of args.input."""
+        from . import container
         args = self.args
-        if not tarfile.is_tarfile(args.input):
-            error('ERROR: Sorry, the path you have provided as input is a file, but not a tar file, and therefore cannot be a .uq file!')
+        if self.source is None or self.tar_path != args.input: self.source = container.open_source(self, args.input)
         self.tar_path = args.input
+        if self.source.kind != container.PLAIN:
+            # a compressed container: the tar is walked by its header fields through the source
+            members = container.walk_tar(self.source)
+            return members, container.read_config(self.source, members)
+        if not tarfile.is_tarfile(args.input):
+            error(container.NOT_A_TAR)
         with tarfile.open(args.input) as t:
             members = {m.name: (m.offset_data, m.size) for m in t.getmembers()}
-            if 'config.json' not in members: error('ERROR: No config.json file was found in your input path! I cannot decode data without it!')
+            if 'config.json' not in members: error(container.NO_CONFIG)
             config = json.loads(t.extractfile('config.json').read().decode())
         return members, config
+
+    @property
+    def inflated_members(self):
+        """BGZF containers: how many of the file's members this session has inflated on the device so far (None for other sources)."""
+        return getattr(self.source, 'inflated_members', None)
 
     def load_tables(self, members, config, rows=None):
         """uq.py:943-973 on the device: the DNA / QUAL tables as (tensor, reads, row bytes) and the QNAME columns, in
@@ -862,6 +920,10 @@ class Session:
         from . import qname
         ctx = self.ctx
         out = out or sys.stdout
+        from . import container
+        # a compressed container is verified whole (every member's length and CRC-32) before the first byte of text leaves
+        self.source, self.tar_path = container.open_source(self, self.args.input), self.args.input
+        if self.source.kind == container.BGZF: self.source.verify_all()
         members, config = self.open_container()
         DNA, QUAL, d_cols = self.load_tables(members, config)
         n = DNA[1]
