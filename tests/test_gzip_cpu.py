@@ -12,6 +12,7 @@ import zlib
 import numpy as np
 import pytest
 
+from deflate_writer import Bits, crafted_invalid, crafted_members, fixed_lit
 from uq_amd import ops, synth
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -212,31 +213,6 @@ def test_host_inflate_checks_trailer():
     assert ops.inflate_member_host(d, 65537, 0)[0] == 12
 
 
-class Bits:
-    """LSB-first bit writer for hand-made deflate streams."""
-
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, value, n):
-        self.v |= (value & ((1 << n) - 1)) << self.n
-        self.n += n
-        return self
-
-    def code(self, code, n):                                # Huffman codes go most significant bit first
-        return self.put(int(format(code, '0%db' % n)[::-1], 2), n)
-
-    def bytes(self):
-        return self.v.to_bytes((self.n + 7) // 8, 'little')
-
-
-def fixed_lit(b, s):
-    if s < 144: b.code(0x30 + s, 8)
-    elif s < 256: b.code(0x190 + s - 144, 9)
-    elif s < 280: b.code(s - 256, 7)
-    else: b.code(0xC0 + s - 280, 8)
-
-
 def crafted():
     """(name, stream, isize, expected status) of hand-made bad streams."""
     out = []
@@ -372,6 +348,11 @@ def test_decoder_fuzz_under_address_sanitizer(tmp_path):
     cases = corrupt_cases(seed=23, count=4000)
     for _, d, data in member_matrix()[::7]:
         cases.append((d, len(data), zlib.crc32(data), data))
+    ncorrupt = len(cases)
+    for _, d, data in crafted_members():                              # valid deflate that zlib's compressor does not write, and
+        cases.append((d, len(data), zlib.crc32(data), data))
+    for _, d, isize, _ in crafted_invalid():                          # its nearest invalid neighbours
+        cases.append((d, isize, 0, None))
     blob = bytearray()
     for stream, isize, crc, data in cases:
         blob += struct.pack('<IIII', len(stream), isize, crc, 0xFFFFFFFF if data is None else len(data)) + stream + (data or b'')
@@ -384,7 +365,11 @@ def test_decoder_fuzz_under_address_sanitizer(tmp_path):
     for (stream, isize, crc, data), line in zip(cases, lines):
         st, right = map(int, line.split())
         assert st != 0 or right, (len(stream), isize)
-    assert sum(1 for l in lines if l.split()[0] != '0') > len(cases) // 2         # the corruptions mostly end in a status
+    assert sum(1 for l in lines[:ncorrupt] if l.split()[0] != '0') > ncorrupt // 2   # the corruptions mostly end in a status
+    for (name, _, _), line in zip(crafted_members(), lines[ncorrupt:]):
+        assert line == '0 1', name
+    for (name, _, _, want), line in zip(crafted_invalid(), lines[ncorrupt + len(crafted_members()):]):
+        assert line == '%d 0' % want, name
 
 
 # ------------------------------------------------------------------ the sharded encoder

@@ -11,6 +11,7 @@ import zlib
 
 import pytest
 
+from deflate_writer import behind_valid_front, crafted_invalid, crafted_members, crafted_streams, gzip_wrap
 from test_gzip_cpu import _gxx, bgzf, gzip_member, raw_deflate
 from uq_amd import ops, synth
 
@@ -267,11 +268,21 @@ def test_stream_decoder_under_address_sanitizer(tmp_path):
     blob = bytearray()
     ncases = 0
     streams = corrupt_streams(seed=41, count=300) + [b for _, b, _ in stream_matrix()[::4]]
+    nold = 3 * len(streams)
+    # valid deflate that zlib's compressor does not write (whole and from random starts), and its invalid neighbours, alone and behind
+    # a valid front
+    valid = [(b, data) for _, b, data in crafted_streams()] + [(gzip_wrap(raw, data), data) for _, raw, data in crafted_members()[::4]]
+    streams += [b for b, _ in valid]
+    streams += [gzip_wrap(raw, b'') for _, raw, _, _ in crafted_invalid()] + [behind_valid_front(raw) for _, raw, isize, _ in crafted_invalid()
+                                                                               if isize == 0]
+    to_the_end = []                          # per case: does it run to the end of its whole stream?
     for s in streams:
+        whole = len(s) <= 150000
         s = s[:150000]
         nb = 8 * len(s)
         for start in (0, rnd.randrange(nb) << 2 | rnd.randrange(3), rnd.randrange(max(1, len(s))) * 8 << 2 | rnd.randrange(2)):
             stop = rnd.choice([(1 << 64) - 1, rnd.randrange(nb + 64)])
+            to_the_end.append(whole and stop == (1 << 64) - 1)
             blob += struct.pack('<QQQ', len(s), start, stop) + s
             ncases += 1
     (tmp_path / 'cases.bin').write_bytes(bytes(blob))
@@ -281,7 +292,15 @@ def test_stream_decoder_under_address_sanitizer(tmp_path):
     lines = r.stdout.split('\n')[:-1]
     assert len(lines) == ncases
     statuses = [int(l.split()[0]) for l in lines]
-    assert any(s == 0 for s in statuses) and any(s == 14 for s in statuses) and sum(1 for s in statuses if s not in (0, 14)) > ncases // 4
+    old = statuses[:nold]
+    assert any(s == 0 for s in old) and any(s == 14 for s in old) and sum(1 for s in old if s not in (0, 14)) > nold // 4
+    # the valid crafted streams from their header: nothing but the end, `stop` or a full slot ends them.  A chunk from a member header
+    # writes bytes, so 65 536 bytes of slot hold 60 000 of output and its few member records, and do not hold more than 65 536.
+    for k, (_, data) in enumerate(valid):
+        st = statuses[nold + 3 * k]
+        assert st in (0, 14), (k, st)
+        if to_the_end[nold + 3 * k] and len(data) <= 60000: assert st == 0, (k, st)
+        if to_the_end[nold + 3 * k] and len(data) > 65536: assert st == 14, (k, st)
 
 
 def _binned(n, p):
