@@ -21,6 +21,9 @@ Where each edge of the issue lives (crafted_members = M, crafted_streams = S, cr
   a literal/length code that is only end-of-block               M lit_only_end_of_block
   HLIT / HDIST / HCLEN minima                                   M hlit_257_hdist_1_hclen_5 (HCLEN 4 leaves only zero lengths, so it has no
                                                                 end-of-block code: I hclen_4_only_zero_lengths)
+  a code-length code that is not complete: one code of one    I precode_only_16_then_16, I precode_only_8_then_ones, I precode_only_0_then_zeros,
+  bit, or none (both decoders: status 4 before any repeat,    I precode_hclen_4_all_zero
+  symbol or end-of-block check)
   HLIT / HDIST / HCLEN maxima                                   M hlit_286_hdist_30_hclen_19
   16 straight after 17 / 18                                     M rle_16_after_17, M rle_16_after_18
   18 with 138                                                   M rle_18_with_138
@@ -832,6 +835,15 @@ def crafted_invalid():
     out.append(('no_end_of_block_code', b.put(0, 32).bytes(), 0, 4))
     b = _dyn_header(Bits(), 257, 1, {18: 1, 0: 1}, zeros(258), hclen=4)                        # 16, 17, 18 and 0 only: nothing but zero lengths
     out.append(('hclen_4_only_zero_lengths', b.put(0, 64).bytes(), 0, 4))
+    # a code-length code of one one-bit code, or of none, is refused as such by both decoders, whatever follows it
+    b = _dyn_header(Bits(), 257, 1, {16: 1}, [(16, 0)])
+    out.append(('precode_only_16_then_16', b.put(0, 32).bytes(), 0, 4))
+    b = _dyn_header(Bits(), 257, 1, {8: 1}, [])
+    out.append(('precode_only_8_then_ones', b.put(0xFFFFFFFF, 32).put(0xFFFFFFFF, 32).bytes(), 0, 4))
+    b = _dyn_header(Bits(), 257, 1, {0: 1}, [])
+    out.append(('precode_only_0_then_zeros', b.put(0, 64).bytes(), 0, 4))
+    b = _dyn_header(Bits(), 257, 1, {}, [], hclen=4)
+    out.append(('precode_hclen_4_all_zero', b.put(0, 64).bytes(), 0, 4))
     for name, raw, isize, _ in out:
         assert zlib_refuses(raw, isize), name
     return out

@@ -12,7 +12,7 @@
 //
 // LDS: UqDeflateLds is about 151 KiB (the block, one match-length byte per position, the head table / parse window / Huffman scratch, the
 // code tables): one workgroup of UQ_DEF_THREADS threads per CU.
-#include "common.h"
+#include "inflate_env.h"
 #include "deflate_core.h"
 #include <vector>
 
@@ -21,8 +21,6 @@
 #define UQ_DEF_SLOT 65536u
 
 namespace {
-
-struct X2nArg { uint32_t v[32]; };
 
 struct DevEnv {
     uint32_t* out;              // the block's slot
@@ -40,7 +38,7 @@ struct DevEnv {
 
 __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_kernel(const uint8_t* __restrict__ in, uint64_t nbytes, uint64_t first_block,
                                                                       uint8_t* __restrict__ slots, uint16_t* __restrict__ dist,
-                                                                      uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2nArg x2n) {
+                                                                      uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2n x2n) {
     __shared__ __attribute__((aligned(16))) UqDeflateLds s;
     __shared__ uint32_t x2n_s[32];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
@@ -110,7 +108,7 @@ template <int WS> __device__ __forceinline__ Vec4 shifted_vec(Vec4 a, Vec4 c, ui
 __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_parts_kernel(const PartBlock* __restrict__ table, const PartSrc* __restrict__ parts,
                                                                             const uint8_t* __restrict__ arena, uint64_t first_block,
                                                                             uint8_t* __restrict__ slots, uint16_t* __restrict__ dist,
-                                                                            uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2nArg x2n) {
+                                                                            uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2n x2n) {
     __shared__ __attribute__((aligned(16))) UqDeflateLds s;
     __shared__ uint32_t x2n_s[32];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
@@ -218,7 +216,7 @@ extern "C" int uq_bgzf_compress(uq_ctx* c, const uint8_t* d_in, uint64_t nbytes,
         uint32_t* offs = (uint32_t*)(w8 + o_offs);
         uint32_t* status = (uint32_t*)(w8 + o_status);
         uint64_t* total = (uint64_t*)(w8 + o_total);
-        X2nArg x2n;
+        X2n x2n;
         uq_crc_x2n_init(x2n.v);
         uint32_t* h_status = new uint32_t[chunk];
         for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
@@ -336,7 +334,7 @@ extern "C" int uq_bgzf_compress_parts(uq_ctx* c, const uq_bgzf_part* h_parts, ui
         UQ_CHECK_HIP(hipMemcpyAsync(src, h_src.data(), h_src.size() * sizeof(PartSrc), hipMemcpyHostToDevice, c->stream));
         UQ_CHECK_HIP(hipMemcpyAsync(arena, h_arena.data(), h_arena.size(), hipMemcpyHostToDevice, c->stream));
         UQ_CHECK_HIP(hipMemsetAsync(pbytes, 0, (size_t)nparts * 8, c->stream));
-        X2nArg x2n;
+        X2n x2n;
         uq_crc_x2n_init(x2n.v);
         std::vector<uint32_t> h_status(chunk);
         for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {

@@ -120,8 +120,6 @@ UQ_DEF_HD uint32_t uq_def_dsym(uint32_t D, uint32_t& ev, uint32_t& en) {
 UQ_DEF_HD uint32_t uq_def_lextra(uint32_t sym) { return sym < 265 || sym == 285 ? 0u : (sym - 261) >> 2; }
 UQ_DEF_HD uint32_t uq_def_dextra(uint32_t sym) { return sym < 4 ? 0u : (sym >> 1) - 1; }
 
-// the order in which the code-length code's lengths are sent
-UQ_DEF_HD uint32_t uq_def_order(uint32_t k) { return (uint8_t)"\x10\x11\x12\x00\x08\x07\x09\x06\x0a\x05\x0b\x04\x0c\x03\x0d\x02\x0e\x01\x0f"[k]; }
 
 UQ_DEF_HD uint32_t uq_def_hash(const uint8_t* p) {
     const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -358,7 +356,7 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
     if (tid == 0) {
         if constexpr (kEmit) uq_def_codes(s->clen, 19, s->ccode);
         uint32_t hclen = 19;
-        while (hclen > 4 && !s->clen[uq_def_order(hclen - 1)]) --hclen;
+        while (hclen > 4 && !s->clen[uq_inf_order(hclen - 1)]) --hclen;
         uint32_t b = 3 + 5 + 5 + 4 + 3 * hclen;
         for (uint32_t k = 0; k < s->nrle; ++k) {
             const uint32_t sym = s->rle[k];
@@ -469,7 +467,7 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
         };
         put(1, 1); put(2, 2);                                           // BFINAL, BTYPE = 10
         put(s->hlit - 257, 5); put(s->hdist - 1, 5); put(s->hclen - 4, 4);
-        for (uint32_t k = 0; k < s->hclen; ++k) put(s->clen[uq_def_order(k)], 3);
+        for (uint32_t k = 0; k < s->hclen; ++k) put(s->clen[uq_inf_order(k)], 3);
         for (uint32_t k = 0; k < s->nrle; ++k) {
             const uint32_t sym = s->rle[k];
             put(s->ccode[sym], s->clen[sym]);

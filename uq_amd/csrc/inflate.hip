@@ -1,9 +1,9 @@
 // inflate.hip -- gzip input: the member scan on the host (uq_gzip_scan) and the inflate of BGZF members on the device
 // (uq_inflate_members, one wave per member), plus the host run of the same decoder on one member (uq_inflate_member_host).
 //
-// The decoder itself is inflate_core.h.  Here it gets its two environments:
-//   device  Src = the member's compressed bytes, 256 at a time, one dword per lane (a coalesced load), words handed to the
-//                 wave-uniform bit reader with v_readlane; Out = the member's whole output (<= 64 KiB) in LDS, so that back-references read
+// The decoder itself is inflate_core.h.  Here it gets its two environments (the sources and the CRC plumbing are inflate_env.h's, shared with
+// inflate_stream.hip):
+//   device  Src = DevSrc<uint32_t>; Out = the member's whole output (<= 64 KiB) in LDS, so that back-references read
 //                 LDS only and never HBM the kernel has just written; matches are copied by the lanes (src = dst - dist + i % dist), the
 //                 output is then CRC-checked by the lanes (per-segment CRCs combined with shift operators) and flushed to HBM with 16-byte
 //                 stores.
@@ -12,35 +12,9 @@
 // LDS against occupancy: 64 KiB of output + 5 KiB of code tables + the 1 KiB CRC table = 71 616 bytes a workgroup of one wave, so two members
 // are in flight per CU (160 KiB).  A 32 KiB window ring would allow four, at the price of flushing and CRC-ing the ring as it wraps; the
 // whole-member buffer keeps the flush one coalesced pass and the CRC one parallel pass (DESIGN.md section 13 has the measurement).
-#include "common.h"
-#include "inflate_core.h"
+#include "inflate_env.h"
 
 namespace {
-
-struct X2n { uint32_t v[32]; };              // x^(2^k) mod the CRC polynomial, passed by value (kernel arguments: scalar loads)
-
-struct DevSrc {
-    const uint8_t* p;
-    uint32_t len, wbase, mine, lane;
-    __device__ void load(uint32_t base) {
-        wbase = base;
-        const uint32_t b = base + 4 * lane;
-        uint32_t v = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (b + k < len) v |= (uint32_t)p[b + k] << (8 * k);
-        mine = v;
-    }
-    __device__ uint32_t word(uint32_t off) {
-        off = __builtin_amdgcn_readfirstlane(off);                       // wave-uniform by construction; this tells the compiler
-        if (off < wbase || off + 4 > wbase + 256) load(off & ~3u);
-        const uint32_t rel = off - wbase, i = rel >> 2, s = (rel & 3) * 8;
-        const uint32_t lo = __builtin_amdgcn_readlane(mine, i);
-        if (!s) return lo;
-        const uint32_t hi = __builtin_amdgcn_readlane(mine, (i + 1) & 63);
-        return (lo >> s) | (hi << (32 - s));
-    }
-};
 
 struct DevOut {
     uint8_t* o;                 // LDS, the member's output
@@ -83,7 +57,7 @@ __global__ __launch_bounds__(64) void inflate_members_kernel(const uint8_t* __re
     if (st == UQ_INF_OK) {
         for (uint32_t e = lane; e < 256; e += 64) crctab[e] = uq_crc_table_entry(e);
         const uint8_t* src = comp + mem.data_offset;
-        DevSrc s{src, (uint32_t)mem.comp_bytes, 0, 0, lane};
+        DevSrc<uint32_t> s{src, (uint32_t)mem.comp_bytes, 0, 0, lane};
         s.load(0);
         DevOut o{obuf, src, lane};
         st = uq_inflate_core(s, (uint32_t)mem.comp_bytes, o, mem.isize, &tab, lane, 64);
@@ -95,18 +69,7 @@ __global__ __launch_bounds__(64) void inflate_members_kernel(const uint8_t* __re
         uint32_t S = (((n + 63) / 64) + 3) & ~3u;
         if (!((S >> 2) & 1)) S += 4;
         const uint32_t lo = min(n, lane * S), hi = min(n, lo + S);
-        uint32_t c = 0, i = lo;
-        for (; i + 4 <= hi; i += 4) {
-            c ^= *(const uint32_t*)(obuf + i);
-            c = crctab[c & 0xFF] ^ (c >> 8);
-            c = crctab[c & 0xFF] ^ (c >> 8);
-            c = crctab[c & 0xFF] ^ (c >> 8);
-            c = crctab[c & 0xFF] ^ (c >> 8);
-        }
-        c = uq_crc0_bytes(crctab, c, obuf + i, hi - i);
-        c = uq_crc_multmodp(uq_crc_shift_op(x2n.v, n - hi), c);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d, 64);
+        const uint32_t c = wave_crc0(crctab, x2n, 0, obuf + lo, hi - lo, n - hi);
         if (uq_crc_finish(x2n.v, c, n) != mem.crc32) st = UQ_INF_CRC_MISMATCH;
     }
     if (st == UQ_INF_OK) {
@@ -123,17 +86,6 @@ __global__ __launch_bounds__(64) void inflate_members_kernel(const uint8_t* __re
     if (lane == 0) status[m] = (uint32_t)st;
 }
 
-struct HostSrc {
-    const uint8_t* p;
-    uint32_t len;
-    uint32_t word(uint32_t off) const {
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < 4; ++k)
-            if ((uint64_t)off + k < len) v |= (uint32_t)p[off + k] << (8 * k);
-        return v;
-    }
-};
-
 struct HostOut {
     uint8_t* o;
     const uint8_t* src;
@@ -145,12 +97,6 @@ struct HostOut {
 
 uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-
-struct CrcTable {
-    uint32_t t[256];
-    CrcTable() { for (uint32_t e = 0; e < 256; ++e) t[e] = uq_crc_table_entry(e); }
-};
-const uint32_t* crc_table() { static const CrcTable tab; return tab.t; }
 
 uint32_t host_crc32(const uint8_t* p, uint64_t n) {
     return uq_crc0_bytes(crc_table(), 0xFFFFFFFFu, p, (uint32_t)n) ^ 0xFFFFFFFFu;
@@ -263,7 +209,7 @@ extern "C" int uq_inflate_member_host(const uint8_t* h_comp, uint64_t comp_bytes
     UQ_REQUIRE(h_status && (h_comp || !comp_bytes) && (h_out || !isize), "uq_inflate_member_host: null argument");
     if (isize > UQ_INF_MAX_OUT || comp_bytes > 0xFFFFFFF0ull) { *h_status = UQ_INF_TOO_LARGE; return 0; }
     UqInflateTables* t = new UqInflateTables();
-    HostSrc s{h_comp, (uint32_t)comp_bytes};
+    HostSrc<uint32_t> s{h_comp, (uint32_t)comp_bytes};
     HostOut o{h_out, h_comp};
     int st = uq_inflate_core(s, (uint32_t)comp_bytes, o, (uint32_t)isize, t, 0, 1);
     delete t;

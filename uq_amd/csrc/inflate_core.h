@@ -1,13 +1,20 @@
-// inflate_core.h -- RFC 1951 (deflate) decoding of one gzip member, shared by the GPU kernel (inflate.hip, one wave per member) and the
-// host entry uq_inflate_member_host (one "lane"), so that the decoder's handling of corrupt input can be exercised on a CPU under
-// AddressSanitizer with the very code the GPU runs.  Plain g++ compiles this header: the qualifiers are guarded.
+// inflate_core.h -- RFC 1951 (deflate) decoding, shared by the GPU kernels and the host entries (one "lane"), so that the decoder's handling of
+// corrupt input can be exercised on a CPU under AddressSanitizer with the very code the GPU runs.  Plain g++ compiles this header: the
+// qualifiers are guarded.  Two decoders are built from it: uq_inflate_core below (one gzip member into a buffer of known size: inflate.hip,
+// one wave per member) and uq_gzs_chunk (inflate_stream.h: a chunk of a gzip file from a speculative start).  Everything a deflate block
+// is made of lives here once, for both: the bit reader (UqBits), the block's code tables from its header (uq_inf_tables, with the rules a
+// set of code lengths must meet: uq_inf_precode_ok, uq_inf_kraft) and a stored block's header (uq_inf_stored_header).  The two symbol loops
+// stay apart: they differ in what bounds the output, in the distance rule and in where a decode may stop.  Each keeps its own copy of the
+// dozen lines that turn a length symbol into (length, distance): as a shared function, in three forms, they made inflate_members_kernel
+// 3 to 7 % slower on the MI355X.
 //
 // Safety contract (every input is hostile):
 //   - the compressed bytes are read only through Src::word(), whose reads are bounded by the member's compressed length; bytes past it
 //     read as zero, and the decoder stops with UQ_INF_TRUNCATED as soon as it has consumed a bit it does not own;
 //   - the output is written only through Out, and only below isize: every literal, match and stored copy is checked against it first;
 //   - every distance is checked against the bytes produced so far;
-//   - over-subscribed code-length sets are rejected, incomplete ones too except the single one-bit code deflate allows;
+//   - over-subscribed code-length sets are rejected, incomplete ones too except the single one-bit code deflate allows (not for the
+//     code-length code, which must be complete: zlib's rule);
 //   - every loop is bounded: a block and a symbol each consume at least one bit, and consumption is checked against the bit budget.
 #pragma once
 #include <stdint.h>
@@ -62,6 +69,36 @@ UQ_INF_HD uint32_t uq_inf_rev(uint32_t code, int len) {
     return r;
 }
 
+// The order in which a dynamic block's header sends the code-length code's lengths (RFC 1951 3.2.7)
+UQ_INF_HD uint32_t uq_inf_order(uint32_t i) {
+    static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    return order[i];
+}
+
+// The rule for a code, given its count of codes of every length 1..15: not over-subscribed, and complete unless it is at most one code of
+// one bit (deflate allows that, for a block with a single distance or none)
+UQ_INF_HD bool uq_inf_kraft(const uint16_t* count) {
+    int left = 1, maxlen = 0;
+    for (int l = 1; l < 16; ++l) {
+        left = (left << 1) - count[l];
+        if (left < 0) return false;
+        if (count[l]) maxlen = l;
+    }
+    return !(left > 0 && maxlen > 1);
+}
+
+// The stricter rule for the code-length code (zlib's): complete.  v: up to 19 three-bit lengths as the header sends them, length i at bits 3i
+UQ_INF_HD bool uq_inf_precode_ok(uint64_t v, int ncode) {
+    int left = 1;
+    for (int l = 1; l < 8; ++l) {
+        int c = 0;
+        for (int i = 0; i < ncode; ++i) c += (int)(((v >> (3 * i)) & 7) == (uint64_t)l);
+        left = 2 * left - c;
+        if (left < 0) return false;
+    }
+    return left == 0;
+}
+
 // Builds the canonical description of the code of n lengths into `h` and clears the primary table `tab` (1 << bits entries).  lane / nlanes:
 // the work is spread over the lanes of a wave (the host passes 0 / 1).  Arrays that are indexed by data live in `h` (LDS on the device),
 // never in registers; `sync()` orders one phase's writes by some lanes before the next phase's reads by others.
@@ -73,17 +110,11 @@ UQ_INF_HD int uq_inf_build(const uint8_t* lens, int n, UqHuff* h, uint16_t* tab,
         h->count[l] = (uint16_t)(l ? c : 0);
     }
     sync.sync();
-    int left = 1, maxlen = 0;
-    uint32_t off = 0;
-    for (int l = 1; l < 16; ++l) {
-        const int c = h->count[l];
-        left = (left << 1) - c;
-        if (left < 0) return UQ_INF_BAD_CODE_LENGTHS;                  // over-subscribed
-        if (c) maxlen = l;
-        if (lane == 0) h->offs[l] = (uint16_t)off;
-        off += (uint32_t)c;
+    if (!uq_inf_kraft(h->count)) return UQ_INF_BAD_CODE_LENGTHS;
+    if (lane == 0) {
+        uint32_t off = 0;
+        for (int l = 1; l < 16; ++l) { h->offs[l] = (uint16_t)off; off += h->count[l]; }
     }
-    if (left > 0 && maxlen > 1) return UQ_INF_BAD_CODE_LENGTHS;        // incomplete (deflate allows one code of one bit, or none)
     for (uint32_t e = lane; e < (1u << bits); e += nlanes) tab[e] = 0;
     sync.sync();
     if (lane == 0)                                                      // symbols in canonical order
@@ -110,25 +141,28 @@ UQ_INF_HD void uq_inf_fill(const UqHuff* h, uint16_t* tab, int bits, uint32_t la
     }
 }
 
-// The bit reader over Src::word(byte offset) = the 4 bytes there, little-endian, zero past the member's end.
-template <class Src>
+// The bit reader over Src::word(byte offset) = the 4 bytes there, little-endian, zero past the data's end.  Off is the type of a byte offset:
+// 32 bits for a BGZF member (fewer registers, and the offset is made wave-uniform with one v_readfirstlane), 64 for a whole file.
+template <class Src, class Off = uint32_t>
 struct UqBits {
     Src& src;
     uint64_t buf;
     uint32_t cnt;       // valid bits in buf
-    uint32_t pos;       // next byte offset to load
-    uint32_t len;       // compressed length in bytes
-    UQ_INF_HD UqBits(Src& s, uint32_t n) : src(s), buf(0), cnt(0), pos(0), len(n) {}
+    Off pos;            // next byte offset to load
+    Off len;            // compressed length in bytes
+    UQ_INF_HD UqBits(Src& s, Off n) : src(s), buf(0), cnt(0), pos(0), len(n) {}
     UQ_INF_HD void refill() {
         if (cnt <= 32) { buf |= (uint64_t)src.word(pos) << cnt; pos += 4; cnt += 32; }
     }
     UQ_INF_HD uint32_t peek(uint32_t n) const { return (uint32_t)buf & ((1u << n) - 1); }
     UQ_INF_HD void drop(uint32_t n) { buf >>= n; cnt -= n; }
     UQ_INF_HD uint32_t get(uint32_t n) { refill(); uint32_t v = peek(n); drop(n); return v; }   // n <= 16
-    UQ_INF_HD bool overrun() const { return 8ull * pos - cnt > 8ull * len; }
-    UQ_INF_HD uint32_t byte_pos() const { return pos - cnt / 8; }                                // after align(): the next unread byte
+    UQ_INF_HD uint64_t bit_pos() const { return 8ull * pos - cnt; }                              // of the next unread bit
+    UQ_INF_HD bool overrun() const { return bit_pos() > 8ull * len; }
+    UQ_INF_HD Off byte_pos() const { return pos - cnt / 8; }                                     // after align(): the next unread byte
     UQ_INF_HD void align() { drop(cnt & 7); }
-    UQ_INF_HD void seek(uint32_t p) { buf = 0; cnt = 0; pos = p; }
+    UQ_INF_HD void seek(Off p) { buf = 0; cnt = 0; pos = p; }
+    UQ_INF_HD void seek_bit(uint64_t b) { seek((Off)(b >> 3)); refill(); drop((uint32_t)(b & 7)); }
 };
 
 // One symbol of code (h, tab): the primary table, or the canonical walk for codes longer than `bits`.  Needs >= 15 bits in the buffer.
@@ -156,6 +190,83 @@ UQ_INF_HD void uq_inf_fixed_lens(uint8_t* lens, uint32_t lane, uint32_t nlanes) 
         lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5;
 }
 
+// One block's code tables, fixed (type 1) or dynamic (type 2, from the header that follows BTYPE): t->lit / hlit and t->dist / hdist ready
+// for uq_inf_decode.  Sync::sync() orders one phase's table writes by some lanes before the next phase's reads by others.  The rules are
+// zlib's: the code-length code complete, the other two as uq_inf_kraft, an end-of-block code present.
+template <class B, class Sync>
+UQ_INF_HD int uq_inf_tables(B& br, uint32_t type, UqInflateTables* t, uint32_t lane, uint32_t nlanes, Sync& sync) {
+    int nlit = 288, ndist = 32;
+    if (type == 1) {
+        uq_inf_fixed_lens(t->lens, lane, nlanes);
+        sync.sync();
+    } else {
+        nlit = (int)br.get(5) + 257;
+        ndist = (int)br.get(5) + 1;
+        const int ncode = (int)br.get(4) + 4;
+        if (nlit > 286 || ndist > 30) return UQ_INF_BAD_COUNTS;
+        // the code-length code's lengths in lens[0, 19)
+        for (uint32_t i = lane; i < 19; i += nlanes) t->lens[i] = 0;
+        sync.sync();
+        uint64_t pc = 0;
+        for (int i = 0; i < ncode; ++i) {
+            const uint32_t v = br.get(3);
+            pc |= (uint64_t)v << (3 * i);
+            if (lane == 0) t->lens[uq_inf_order((uint32_t)i)] = (uint8_t)v;
+        }
+        if (br.overrun()) return UQ_INF_TRUNCATED;
+        if (!uq_inf_precode_ok(pc, ncode)) return UQ_INF_BAD_CODE_LENGTHS;
+        sync.sync();
+        int st = uq_inf_build(t->lens, 19, &t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes, sync);
+        if (st) return st;
+        uq_inf_fill(&t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes);
+        sync.sync();
+        // nlit + ndist code lengths; every iteration consumes >= 1 bit
+        int n = 0, prev = -1;
+        while (n < nlit + ndist) {
+            br.refill();
+            const int sym = uq_inf_decode(br, &t->hclen, t->clen, UQ_INF_CLEN_BITS);
+            if (br.overrun()) return UQ_INF_TRUNCATED;
+            if (sym < 0) return UQ_INF_BAD_SYMBOL;
+            int val = 0, rep = 1;
+            if (sym < 16) { val = sym; prev = sym; }
+            else if (sym == 16) { if (prev < 0) return UQ_INF_BAD_REPEAT; val = prev; rep = 3 + (int)br.get(2); }
+            else if (sym == 17) { rep = 3 + (int)br.get(3); }
+            else { rep = 11 + (int)br.get(7); }
+            if (sym == 17 || sym == 18) prev = 0;
+            if (n + rep > nlit + ndist) return UQ_INF_BAD_REPEAT;
+            if (lane == 0) for (int k = 0; k < rep; ++k) t->lens[n + k] = (uint8_t)val;
+            n += rep;
+        }
+        if (br.overrun()) return UQ_INF_TRUNCATED;
+        sync.sync();
+        // the distance lengths go to lens[288...]: the fixed layout, so that one fill serves both forms
+        if (lane == 0) for (int k = ndist - 1; k >= 0; --k) t->lens[288 + k] = t->lens[nlit + k];
+        sync.sync();
+        if (t->lens[256] == 0) return UQ_INF_BAD_CODE_LENGTHS;           // no end-of-block code
+    }
+    int st = uq_inf_build(t->lens, nlit, &t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes, sync);
+    if (st) return st;
+    st = uq_inf_build(t->lens + 288, ndist, &t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes, sync);
+    if (st) return st;
+    uq_inf_fill(&t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes);
+    uq_inf_fill(&t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes);
+    sync.sync();
+    return UQ_INF_OK;
+}
+
+// A stored block's LEN / NLEN (the reader byte-aligned at LEN): *len = LEN, *at = the byte offset of the block's first byte.  The whole block
+// lies inside the data.
+template <class Src, class Off>
+UQ_INF_HD int uq_inf_stored_header(UqBits<Src, Off>& br, uint32_t* len, Off* at) {
+    const uint32_t l = br.get(16), nl = br.get(16);
+    if (br.overrun()) return UQ_INF_TRUNCATED;
+    if (l != (~nl & 0xFFFFu)) return UQ_INF_BAD_STORED_LEN;
+    *len = l;
+    *at = br.byte_pos();
+    if ((uint64_t)*at + l > br.len) return UQ_INF_TRUNCATED;
+    return UQ_INF_OK;
+}
+
 // Inflates one raw deflate stream of `clen` bytes into exactly `isize` bytes.
 //   Out::put(pos, byte)               one literal at output offset pos (< isize)
 //   Out::copy(pos, dist, len)         bytes [pos, pos + len) from pos - dist (dist <= pos, pos + len <= isize; may overlap)
@@ -171,11 +282,9 @@ UQ_INF_HD int uq_inflate_core(Src& src, uint32_t clen, Out& out, uint32_t isize,
         const uint32_t type = hdr >> 1;
         if (type == 0) {
             br.align();
-            const uint32_t l = br.get(16), nl = br.get(16);
-            if (br.overrun()) return UQ_INF_TRUNCATED;
-            if (l != (~nl & 0xFFFFu)) return UQ_INF_BAD_STORED_LEN;
-            const uint32_t at = br.byte_pos();
-            if ((uint64_t)at + l > clen) return UQ_INF_TRUNCATED;
+            uint32_t l, at;
+            const int st = uq_inf_stored_header(br, &l, &at);
+            if (st) return st;
             if ((uint64_t)pos + l > isize) return UQ_INF_OUTPUT_OVERFLOW;
             out.stored(pos, at, l);
             pos += l;
@@ -183,60 +292,8 @@ UQ_INF_HD int uq_inflate_core(Src& src, uint32_t clen, Out& out, uint32_t isize,
         } else if (type == 3) {
             return UQ_INF_BAD_BLOCK_TYPE;
         } else {
-            int nlit = 288, ndist = 32;
-            if (type == 1) {
-                uq_inf_fixed_lens(t->lens, lane, nlanes);
-                out.sync();
-            } else {
-                nlit = (int)br.get(5) + 257;
-                ndist = (int)br.get(5) + 1;
-                const int ncode = (int)br.get(4) + 4;
-                if (nlit > 286 || ndist > 30) return UQ_INF_BAD_COUNTS;
-                // the code-length code's lengths in lens[0, 19) (read in the permuted order of RFC 1951 3.2.7)
-                static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-                for (uint32_t i = lane; i < 19; i += nlanes) t->lens[i] = 0;
-                out.sync();
-                for (int i = 0; i < ncode; ++i) {
-                    const uint32_t v = br.get(3);
-                    if (lane == 0) t->lens[order[i]] = (uint8_t)v;
-                }
-                if (br.overrun()) return UQ_INF_TRUNCATED;
-                out.sync();
-                int st = uq_inf_build(t->lens, 19, &t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes, out);
-                if (st) return st;
-                uq_inf_fill(&t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes);
-                out.sync();
-                // nlit + ndist code lengths; every iteration consumes >= 1 bit
-                int n = 0, prev = -1;
-                while (n < nlit + ndist) {
-                    br.refill();
-                    const int sym = uq_inf_decode(br, &t->hclen, t->clen, UQ_INF_CLEN_BITS);
-                    if (br.overrun()) return UQ_INF_TRUNCATED;
-                    if (sym < 0) return UQ_INF_BAD_SYMBOL;
-                    int val = 0, rep = 1;
-                    if (sym < 16) { val = sym; prev = sym; }
-                    else if (sym == 16) { if (prev < 0) return UQ_INF_BAD_REPEAT; val = prev; rep = 3 + (int)br.get(2); }
-                    else if (sym == 17) { rep = 3 + (int)br.get(3); }
-                    else { rep = 11 + (int)br.get(7); }
-                    if (sym == 17 || sym == 18) prev = 0;
-                    if (n + rep > nlit + ndist) return UQ_INF_BAD_REPEAT;
-                    if (lane == 0) for (int k = 0; k < rep; ++k) t->lens[n + k] = (uint8_t)val;
-                    n += rep;
-                }
-                if (br.overrun()) return UQ_INF_TRUNCATED;
-                out.sync();
-                // the distance lengths go to lens[288...]: the fixed layout, so that one fill serves both forms
-                if (lane == 0) for (int k = ndist - 1; k >= 0; --k) t->lens[288 + k] = t->lens[nlit + k];
-                out.sync();
-                if (t->lens[256] == 0) return UQ_INF_BAD_CODE_LENGTHS;   // no end-of-block code
-            }
-            int st = uq_inf_build(t->lens, nlit, &t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes, out);
+            int st = uq_inf_tables(br, type, t, lane, nlanes, out);
             if (st) return st;
-            st = uq_inf_build(t->lens + 288, ndist, &t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes, out);
-            if (st) return st;
-            uq_inf_fill(&t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes);
-            uq_inf_fill(&t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes);
-            out.sync();
             for (;;) {                                                  // symbols: each consumes >= 1 bit, checked against the budget
                 br.refill();
                 const int sym = uq_inf_decode(br, &t->hlit, t->lit, UQ_INF_LIT_BITS);
@@ -248,7 +305,7 @@ UQ_INF_HD int uq_inflate_core(Src& src, uint32_t clen, Out& out, uint32_t isize,
                     continue;
                 }
                 if (sym == 256) break;
-                const int li = sym - 257;
+                const int li = sym - 257;                               // the match: uq_gzs_chunk has the same lines (see the file head)
                 if (li >= 29) return UQ_INF_BAD_SYMBOL;
                 uint32_t length;
                 if (li < 8) length = 3 + (uint32_t)li;

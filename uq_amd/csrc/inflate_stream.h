@@ -4,6 +4,8 @@
 // unknown 32 KiB before the chunk coming out as *markers*; the chain of chunk ends and starts is checked (that is where correctness comes
 // from); the markers are resolved once the predecessors' output is known; CRC-32 and ISIZE of every member are checked at the end.
 // Shared by the GPU kernels (inflate_stream.hip, one wave per chunk) and the host entry (one "lane"); plain g++ compiles this header.
+// What a deflate block is made of (bit reader, code tables and their rules, stored header) is inflate_core.h's, the same code as the
+// member decoder's; this header owns the finder, the chunk's output (ring, slot) and the loop over units, blocks and symbols.
 //
 // Units and their canonical positions (one per unit, so that the chain check is an exact equality of (position, kind)):
 //   UQ_GZS_MEMBER        a gzip member header: 8 x the byte offset of its 1f 8b;
@@ -67,28 +69,6 @@ struct UqGzsMember {
     uint64_t reserved;
 };
 
-// ---- the bit reader, 64-bit offsets
-template <class Src>
-struct UqBits64 {
-    Src& src;
-    uint64_t buf;
-    uint32_t cnt;
-    uint64_t pos, len;
-    UQ_INF_HD UqBits64(Src& s, uint64_t n) : src(s), buf(0), cnt(0), pos(0), len(n) {}
-    UQ_INF_HD void refill() {
-        if (cnt <= 32) { buf |= (uint64_t)src.word(pos) << cnt; pos += 4; cnt += 32; }
-    }
-    UQ_INF_HD uint32_t peek(uint32_t n) const { return (uint32_t)buf & ((1u << n) - 1); }
-    UQ_INF_HD void drop(uint32_t n) { buf >>= n; cnt -= n; }
-    UQ_INF_HD uint32_t get(uint32_t n) { refill(); uint32_t v = peek(n); drop(n); return v; }
-    UQ_INF_HD bool overrun() const { return 8 * pos - cnt > 8 * len; }
-    UQ_INF_HD uint64_t bit_pos() const { return 8 * pos - cnt; }
-    UQ_INF_HD uint64_t byte_pos() const { return pos - cnt / 8; }
-    UQ_INF_HD void align() { drop(cnt & 7); }
-    UQ_INF_HD void seek(uint64_t p) { buf = 0; cnt = 0; pos = p; }
-    UQ_INF_HD void seek_bit(uint64_t b) { seek(b >> 3); refill(); drop((uint32_t)(b & 7)); }
-};
-
 // 64 bits of the data from bit offset `bit` (zero past the end)
 template <class Src>
 UQ_INF_HD uint64_t uq_gzs_bits64(Src& s, uint64_t bit) {
@@ -96,18 +76,6 @@ UQ_INF_HD uint64_t uq_gzs_bits64(Src& s, uint64_t bit) {
     const uint32_t sh = (uint32_t)(bit & 7);
     const uint64_t lo = (uint64_t)s.word(b) | ((uint64_t)s.word(b + 4) << 32);
     return sh ? (lo >> sh) | ((uint64_t)s.word(b + 8) << (64 - sh)) : lo;
-}
-
-// Kraft check of up to 19 three-bit code-length-code lengths packed in v (length i at bits 3i): the code must be complete (zlib's rule for it)
-UQ_INF_HD bool uq_gzs_precode_ok(uint64_t v, int ncode) {
-    int left = 1;
-    for (int l = 1; l < 8; ++l) {
-        int c = 0;
-        for (int i = 0; i < ncode; ++i) c += (int)(((v >> (3 * i)) & 7) == (uint64_t)l);
-        left = 2 * left - c;
-        if (left < 0) return false;
-    }
-    return left == 0;
 }
 
 // ---- the start finder.  Cheap tests first: the member magic, a stored block's LEN / NLEN, a dynamic header's BTYPE, counts and precode
@@ -126,7 +94,7 @@ UQ_INF_HD uint32_t uq_gzs_probe_cheap(Src& s, uint64_t n, uint64_t bit) {
     const uint64_t v = uq_gzs_bits64(s, bit);
     if ((v >> 1 & 3) == 2 && (v >> 3 & 31) <= 29 && (v >> 8 & 31) <= 29) {
         const int ncode = (int)(v >> 13 & 15) + 4;
-        if (uq_gzs_precode_ok(uq_gzs_bits64(s, bit + 17), ncode)) m |= 4;
+        if (uq_inf_precode_ok(uq_gzs_bits64(s, bit + 17), ncode)) m |= 4;
     }
     return m;
 }
@@ -139,17 +107,11 @@ struct UqGzsProbe {
     uint16_t count[16];
 };
 
-// Kraft rule of uq_inf_build on lens[0, n): not over-subscribed, complete unless at most one code of one bit
+// uq_inf_kraft on lens[0, n)
 UQ_INF_HD bool uq_gzs_kraft(const uint8_t* lens, int n, uint16_t* count) {
     for (int l = 0; l < 16; ++l) count[l] = 0;
     for (int i = 0; i < n; ++i) count[lens[i]]++;
-    int left = 1, maxlen = 0;
-    for (int l = 1; l < 16; ++l) {
-        left = 2 * left - count[l];
-        if (left < 0) return false;
-        if (count[l]) maxlen = l;
-    }
-    return !(left > 0 && maxlen > 1);
+    return uq_inf_kraft(count);
 }
 
 // The full dynamic header at `bit`: the code lengths decode without a bad repeat, the literal/length and distance codes are valid, the
@@ -158,10 +120,9 @@ template <class Src>
 UQ_INF_HD bool uq_gzs_probe_dynamic(Src& s, uint64_t n, uint64_t bit, UqGzsProbe* p) {
     const uint64_t v = uq_gzs_bits64(s, bit);
     const int nlit = (int)(v >> 3 & 31) + 257, ndist = (int)(v >> 8 & 31) + 1, ncode = (int)(v >> 13 & 15) + 4;
-    static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
     const uint64_t pc = uq_gzs_bits64(s, bit + 17);
     for (int i = 0; i < 19; ++i) p->clen[i] = 0;
-    for (int i = 0; i < ncode; ++i) p->clen[order[i]] = (uint8_t)(pc >> (3 * i) & 7);
+    for (int i = 0; i < ncode; ++i) p->clen[uq_inf_order((uint32_t)i)] = (uint8_t)(pc >> (3 * i) & 7);
     for (int l = 0; l < 8; ++l) p->count[l] = 0;
     for (int i = 0; i < 19; ++i) p->count[p->clen[i]]++;
     int offs[8];
@@ -355,76 +316,13 @@ struct UqGzsOut {
     }
 };
 
-// ---- the block decoder: one block's tables (fixed or dynamic, BTYPE already consumed), then its symbols up to end-of-block.
-// The lengths code's rules are zlib's: over-subscribed sets are rejected, incomplete ones too except a single one-bit code (none at all
-// for distances), the code-length code must be complete.
-template <class B, class Sync>
-UQ_INF_HD int uq_gzs_tables(B& br, uint32_t type, UqInflateTables* t, uint32_t lane, uint32_t nlanes, Sync& sync) {
-    int nlit = 288, ndist = 32;
-    if (type == 1) {
-        uq_inf_fixed_lens(t->lens, lane, nlanes);
-        sync.sync();
-    } else {
-        nlit = (int)br.get(5) + 257;
-        ndist = (int)br.get(5) + 1;
-        const int ncode = (int)br.get(4) + 4;
-        if (nlit > 286 || ndist > 30) return UQ_INF_BAD_COUNTS;
-        static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        for (uint32_t i = lane; i < 19; i += nlanes) t->lens[i] = 0;
-        sync.sync();
-        uint64_t pc = 0;
-        for (int i = 0; i < ncode; ++i) {
-            const uint32_t v = br.get(3);
-            pc |= (uint64_t)v << (3 * i);
-            if (lane == 0) t->lens[order[i]] = (uint8_t)v;
-        }
-        if (br.overrun()) return UQ_INF_TRUNCATED;
-        if (!uq_gzs_precode_ok(pc, ncode)) return UQ_INF_BAD_CODE_LENGTHS;
-        sync.sync();
-        int st = uq_inf_build(t->lens, 19, &t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes, sync);
-        if (st) return st;
-        uq_inf_fill(&t->hclen, t->clen, UQ_INF_CLEN_BITS, lane, nlanes);
-        sync.sync();
-        int n = 0, prev = -1;
-        while (n < nlit + ndist) {
-            br.refill();
-            const int sym = uq_inf_decode(br, &t->hclen, t->clen, UQ_INF_CLEN_BITS);
-            if (br.overrun()) return UQ_INF_TRUNCATED;
-            if (sym < 0) return UQ_INF_BAD_SYMBOL;
-            int val = 0, rep = 1;
-            if (sym < 16) { val = sym; prev = sym; }
-            else if (sym == 16) { if (prev < 0) return UQ_INF_BAD_REPEAT; val = prev; rep = 3 + (int)br.get(2); }
-            else if (sym == 17) { rep = 3 + (int)br.get(3); }
-            else { rep = 11 + (int)br.get(7); }
-            if (sym == 17 || sym == 18) prev = 0;
-            if (n + rep > nlit + ndist) return UQ_INF_BAD_REPEAT;
-            if (lane == 0) for (int k = 0; k < rep; ++k) t->lens[n + k] = (uint8_t)val;
-            n += rep;
-        }
-        if (br.overrun()) return UQ_INF_TRUNCATED;
-        sync.sync();
-        if (lane == 0) for (int k = ndist - 1; k >= 0; --k) t->lens[288 + k] = t->lens[nlit + k];
-        sync.sync();
-        if (t->lens[256] == 0) return UQ_INF_BAD_CODE_LENGTHS;
-    }
-    int st = uq_inf_build(t->lens, nlit, &t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes, sync);
-    if (st) return st;
-    st = uq_inf_build(t->lens + 288, ndist, &t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes, sync);
-    if (st) return st;
-    uq_inf_fill(&t->hlit, t->lit, UQ_INF_LIT_BITS, lane, nlanes);
-    uq_inf_fill(&t->hdist, t->dist, UQ_INF_DIST_BITS, lane, nlanes);
-    sync.sync();
-    return UQ_INF_OK;
-}
-
 // A stored block's body from its LEN field (the reader byte-aligned).  *pos advances.
 template <class B, class Src, class Out>
-UQ_INF_HD int uq_gzs_copy_block(B& br, Src& src, uint64_t n, Out& out, uint64_t* pos) {
-    const uint32_t l = br.get(16), nl = br.get(16);
-    if (br.overrun()) return UQ_INF_TRUNCATED;
-    if (l != (~nl & 0xFFFFu)) return UQ_INF_BAD_STORED_LEN;
-    const uint64_t at = br.byte_pos();
-    if (at + l > n) return UQ_INF_TRUNCATED;
+UQ_INF_HD int uq_gzs_copy_block(B& br, Src& src, Out& out, uint64_t* pos) {
+    uint32_t l;
+    uint64_t at;
+    const int st = uq_inf_stored_header(br, &l, &at);
+    if (st) return st;
     for (uint32_t d = 0; d < l; d += UQ_GZS_GRANULE) {
         const uint32_t k = l - d < UQ_GZS_GRANULE ? l - d : UQ_GZS_GRANULE;
         if (!out.reserve(*pos, k)) return UQ_GZS_OVERFLOW;
@@ -444,7 +342,7 @@ UQ_INF_HD void uq_gzs_chunk(Src& src, uint64_t n, UqGzsChunk* c, uint16_t* ring,
     uint64_t ubit = start >> 2;
     int ukind = (int)(start & 3);
     UqGzsOut<Env> out(ring, (uint8_t*)(uintptr_t)c->slot, c->cap, ukind == UQ_GZS_MEMBER, lane, nlanes, env);
-    UqBits64<Src> br(src, n);
+    UqBits<Src, uint64_t> br(src, n);
     uint64_t pos = 0, mbase = 0, end = UQ_GZS_NONE;
     bool known = false, first = true;
     int st = UQ_INF_OK;
@@ -462,7 +360,7 @@ UQ_INF_HD void uq_gzs_chunk(Src& src, uint64_t n, UqGzsChunk* c, uint16_t* ring,
         } else if (ukind == UQ_GZS_UNCOMPRESSED) {
             br.seek(ubit >> 3);
             err = ubit >> 3;
-            st = uq_gzs_copy_block(br, src, n, out, &pos);
+            st = uq_gzs_copy_block(br, src, out, &pos);
             if (st) goto done;
         } else {
             br.seek_bit(ubit);
@@ -490,12 +388,12 @@ UQ_INF_HD void uq_gzs_chunk(Src& src, uint64_t n, UqGzsChunk* c, uint16_t* ring,
             final = hdr & 1;
             if (type == 0) {
                 br.align();
-                st = uq_gzs_copy_block(br, src, n, out, &pos);
+                st = uq_gzs_copy_block(br, src, out, &pos);
                 if (st) goto done;
                 continue;
             }
             if (type == 3) { st = UQ_INF_BAD_BLOCK_TYPE; goto done; }
-            st = uq_gzs_tables(br, type, t, lane, nlanes, env);
+            st = uq_inf_tables(br, type, t, lane, nlanes, env);
             if (st) goto done;
             for (;;) {                                                  // symbols: each consumes >= 1 bit
                 br.refill();
@@ -508,7 +406,7 @@ UQ_INF_HD void uq_gzs_chunk(Src& src, uint64_t n, UqGzsChunk* c, uint16_t* ring,
                     continue;
                 }
                 if (sym == 256) break;
-                const int li = sym - 257;
+                const int li = sym - 257;                               // the match: uq_inflate_core has the same lines
                 if (li >= 29) { st = UQ_INF_BAD_SYMBOL; goto done; }
                 uint32_t length;
                 if (li < 8) length = 3 + (uint32_t)li;

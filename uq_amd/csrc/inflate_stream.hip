@@ -17,14 +17,12 @@
 #include <vector>
 #include <algorithm>
 #include <stdlib.h>
-#include "common.h"
+#include "inflate_env.h"
 #include "inflate_stream.h"
 
 struct uq_gzip_stream;
 
 namespace {
-
-struct X2n { uint32_t v[32]; };
 
 const char* gzs_status_text(uint32_t st) {
     switch (st) {
@@ -45,49 +43,6 @@ const char* gzs_status_text(uint32_t st) {
 }
 
 // ------------------------------------------------------------------ device
-__device__ __forceinline__ uint64_t uniform64(uint64_t x) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
-    return (uint64_t)hi << 32 | lo;
-}
-
-// the wave-uniform source of the chunk decoder: 256 bytes at a time, one dword per lane, handed out by v_readlane (as inflate.hip's DevSrc)
-struct DevSrc64 {
-    const uint8_t* p;
-    uint64_t len, wbase;
-    uint32_t mine, lane;
-    __device__ void load(uint64_t base) {
-        wbase = base;
-        const uint64_t b = base + 4 * lane;
-        uint32_t v = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k)
-            if (b + k < len) v |= (uint32_t)p[b + k] << (8 * k);
-        mine = v;
-    }
-    __device__ uint32_t word(uint64_t off) {
-        off = uniform64(off);
-        if (off < wbase || off + 4 > wbase + 256) load(off & ~3ull);
-        const uint32_t rel = (uint32_t)(off - wbase), i = rel >> 2, s = (rel & 3) * 8;
-        const uint32_t lo = __builtin_amdgcn_readlane(mine, i);
-        if (!s) return lo;
-        const uint32_t hi = __builtin_amdgcn_readlane(mine, (i + 1) & 63);
-        return (lo >> s) | (hi << (32 - s));
-    }
-    __device__ uint32_t byte(uint64_t o) const { return o < len ? p[o] : 0u; }         // per lane (stored blocks)
-};
-
-// the finder's per-lane source
-struct LaneSrc {
-    const uint8_t* p;
-    uint64_t len;
-    __device__ uint32_t word(uint64_t off) const {
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < 4; ++k)
-            if (off + k < len) v |= (uint32_t)p[off + k] << (8 * k);
-        return v;
-    }
-};
-
 struct DevEnv {
     __device__ void order() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
     __device__ bool any(bool b) { return __ballot(b) != 0; }
@@ -101,7 +56,7 @@ __global__ __launch_bounds__(64) void gzs_find_kernel(const uint8_t* __restrict_
     const uint32_t lane = threadIdx.x;
     const uint64_t k = (uint64_t)blockIdx.x + 1;
     const uint64_t lo = 8 * k * chunk_bytes, hi = min(8 * (k + 1) * chunk_bytes, 8 * n);
-    LaneSrc s{comp, n};
+    HostSrc<uint64_t> s{comp, n};
     uint64_t res = UQ_GZS_NONE;
     for (uint64_t base = lo; base < hi; base += 64) {
         const uint64_t b = base + lane;
@@ -132,7 +87,7 @@ __global__ __launch_bounds__(64) void gzs_decode_kernel(const uint8_t* __restric
     const uint32_t lane = threadIdx.x;
     for (uint32_t e = lane; e < 256; e += 64) crctab[e] = uq_crc_table_entry(e);
     __syncthreads();
-    DevSrc64 s{comp, n, 0, 0, lane};
+    DevSrc<uint64_t> s{comp, n, 0, 0, lane};
     s.load(0);
     DevEnv env;
     uq_gzs_chunk(s, n, &chunks[todo[blockIdx.x]], ring, &tab, crctab, lane, 64u, env);
@@ -228,17 +183,7 @@ __global__ __launch_bounds__(64) void gzs_crc_pieces_kernel(const uint8_t* __res
     uint32_t c = 0;
     uint64_t i = lo;
     for (; i < hi && ((uintptr_t)(b + i) & 3); ++i) c = tab[(c ^ b[i]) & 0xFF] ^ (c >> 8);
-    for (; i + 4 <= hi; i += 4) {
-        c ^= *(const uint32_t*)(b + i);
-        c = tab[c & 0xFF] ^ (c >> 8);
-        c = tab[c & 0xFF] ^ (c >> 8);
-        c = tab[c & 0xFF] ^ (c >> 8);
-        c = tab[c & 0xFF] ^ (c >> 8);
-    }
-    for (; i < hi; ++i) c = tab[(c ^ b[i]) & 0xFF] ^ (c >> 8);
-    c = uq_crc_multmodp(uq_crc_shift_op(x2n.v, p.len - hi), c);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c ^= __shfl_xor(c, d, 64);
+    c = wave_crc0(tab, x2n, c, b + i, (uint32_t)(hi - i), p.len - hi);
     if (lane == 0) crc[blockIdx.x] = c;
 }
 
@@ -258,30 +203,12 @@ __global__ __launch_bounds__(64) void gzs_crc_members_kernel(const GzsPiece* __r
 }
 
 // ------------------------------------------------------------------ host
-struct HostSrc64 {
-    const uint8_t* p;
-    uint64_t len;
-    uint32_t word(uint64_t off) const {
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < 4; ++k)
-            if (off + k < len) v |= (uint32_t)p[off + k] << (8 * k);
-        return v;
-    }
-    uint32_t byte(uint64_t o) const { return o < len ? p[o] : 0u; }
-};
-
 struct HostEnv {
     void order() {}
     bool any(bool b) { return b; }
     void sync() {}
     void store16(uint8_t* d, const uint32_t* w) { memcpy(d, w, 16); }
 };
-
-struct CrcTab {
-    uint32_t t[256];
-    CrcTab() { for (uint32_t e = 0; e < 256; ++e) t[e] = uq_crc_table_entry(e); }
-};
-const uint32_t* crc_tab() { static const CrcTab tab; return tab.t; }
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -386,11 +313,11 @@ int decode_round(uq_gzip_stream* s, const std::vector<uint32_t>& todo) {
         UQ_CHECK_HIP(hipFreeAsync(d_todo, st));
         UQ_CHECK_HIP(hipStreamSynchronize(st));
     } else {
-        HostSrc64 src{s->comp, s->n};
+        HostSrc<uint64_t> src{s->comp, s->n};
         HostEnv env;
         UqInflateTables* t = new UqInflateTables();
         uint16_t* ring = new uint16_t[UQ_GZS_RING];
-        for (uint32_t k : todo) uq_gzs_chunk(src, s->n, &s->ch[k], ring, t, crc_tab(), 0u, 1u, env);
+        for (uint32_t k : todo) uq_gzs_chunk(src, s->n, &s->ch[k], ring, t, crc_table(), 0u, 1u, env);
         delete[] ring;
         delete t;
     }
@@ -526,7 +453,7 @@ int begin_common(uq_gzip_stream* s, uint64_t chunk_bytes, const uint64_t* h_star
                 UQ_CHECK_HIP(hipFreeAsync(d_found, s->ctx->stream));
                 UQ_CHECK_HIP(hipStreamSynchronize(s->ctx->stream));
             } else {
-                HostSrc64 src{s->comp, n};
+                HostSrc<uint64_t> src{s->comp, n};
                 UqGzsProbe p;
                 for (uint64_t k = 1; k < nch; ++k) found[k] = uq_gzs_find(src, n, 8 * k * chunk_bytes, 8 * (k + 1) * chunk_bytes, &p);
             }
@@ -666,7 +593,7 @@ int finish_host(uq_gzip_stream* s, uint8_t* h_out, uint32_t* h_status, uint64_t*
         uint32_t c = 0;
         for (uint64_t x = a; x < b; x += 1u << 30) {
             const uint32_t l = (uint32_t)std::min<uint64_t>(1u << 30, b - x);
-            c = uq_crc_multmodp(uq_crc_shift_op(x2n, l), c) ^ uq_crc0_bytes(crc_tab(), 0, h_out + x, l);
+            c = uq_crc_multmodp(uq_crc_shift_op(x2n, l), c) ^ uq_crc0_bytes(crc_table(), 0, h_out + x, l);
         }
         if (uq_crc_finish(x2n, c, b - a) != s->mem[m].crc32) return file_error(h_status, h_bad, UQ_INF_CRC_MISMATCH, s->mem[m].trailer);
     }
