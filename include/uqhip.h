@@ -526,8 +526,12 @@ int uq_bgzf_bound(uint64_t nbytes, uint64_t* h_bound);
 /* uq_bgzf_compress: d_in[0, nbytes) (device) as a BGZF stream into d_out (device, out_capacity bytes): one member per 65 280 bytes of input,
  * compressed one workgroup per block, in chunks of blocks (the workspace, from the context's scratch pool, is bounded by the chunk); the
  * members are placed at 64-bit offsets.  flags & UQ_BGZF_EOF: the 28-byte BGZF EOF member is appended.  *h_out_bytes = the bytes written.
+ * flags & UQ_BGZF_LEVEL2: the compressor's level 2 (more match candidates per position and a lazy parse: smaller members, more time);
+ * without it level 1, whose bytes are what they always were.  At either level a member's bytes depend on its input bytes and the level
+ * only, and the bounds hold.  Any other flag bit is an error.
  * A block that fails, or a capacity that is too small, is an error naming the block.  Synchronises the context's stream. */
 #define UQ_BGZF_EOF 1u
+#define UQ_BGZF_LEVEL2 2u
 int uq_bgzf_compress(uq_ctx* ctx, const uint8_t* d_in, uint64_t nbytes, uint8_t* d_out, uint64_t out_capacity, uint64_t* h_out_bytes,
                      uint32_t flags);
 /* uq_bgzf_compress_parts: several buffers as one run of BGZF members (what the `--gz` container writer calls once for all tar members).
@@ -552,6 +556,9 @@ int uq_bgzf_parts_bound(const uq_bgzf_part* h_parts, uint32_t nparts, uint64_t* 
  * *h_out_bytes = its size.  *h_status = 0, 1 (the member needs more than `capacity` bytes: nothing but zeros written) or 2 (nbytes too large). */
 int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
                                 uint32_t* h_status);
+/* uq_bgzf_compress_block_host_l: the same with flags: 0 (level 1) or UQ_BGZF_LEVEL2; any other bit is an error. */
+int uq_bgzf_compress_block_host_l(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
+                                  uint32_t* h_status, uint32_t flags);
 
 /* ---- the size of a buffer as BGZF, without writing it (an extension: what `--test --device-compressor` sizes its candidates with).
  * For the byte string B = prefix || data, S(B) = the sum, over the consecutive 65 280-byte blocks of B, of the size of the member
@@ -565,6 +572,12 @@ int uq_deflate_size(uq_ctx* ctx, const uint8_t* h_prefix, uint32_t prefix_bytes,
                     uint32_t* d_status);
 /* uq_deflate_size_host: the same code on the CPU over host bytes: *h_total = S(h_prefix || h_data). */
 int uq_deflate_size_host(const uint8_t* h_prefix, uint32_t prefix_bytes, const uint8_t* h_data, uint64_t nbytes, uint64_t* h_total);
+/* uq_deflate_size_l, uq_deflate_size_host_l: the same with flags: 0 (level 1) or UQ_BGZF_LEVEL2 (S over the members level 2 writes); any
+ * other bit is an error. */
+int uq_deflate_size_l(uq_ctx* ctx, const uint8_t* h_prefix, uint32_t prefix_bytes, const uint8_t* d_data, uint64_t nbytes, uint64_t* d_total,
+                      uint32_t* d_status, uint32_t flags);
+int uq_deflate_size_host_l(const uint8_t* h_prefix, uint32_t prefix_bytes, const uint8_t* h_data, uint64_t nbytes, uint64_t* h_total,
+                           uint32_t flags);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BGZF-compressed containers (`--gz`): sizes, the parts entry against what it replaces, the CLI both ways, the host routes.
 
-    python tools/bench_container.py [--reads 10000000] [--binned-reads 2000000] [--dir /dev/shm] [--reps 5] [--skip-gzip6]
+    python tools/bench_container.py [--reads 10000000] [--binned-reads 2000000] [--dir /dev/shm] [--reps 5] [--skip-gzip6] [--level {1,2}]
 
 Two corpora, each encoded with all tables raw: bench.py's reads (synth-v1, 150 bp) and the `binned_fastq` corpus of tools/bench_inflate.py,
 whose ratios are the realistic ones.  Every GPU step runs in a child process under its own time limit; the first failure stops the run.
@@ -13,7 +13,7 @@ whose ratios are the realistic ones.  Every GPU step runs in a child process und
   verdicts one PASS / FAIL per bar of DESIGN.md section 17 (in the JSON under "verdicts", and on stderr as the run goes);
   host     the routes a user takes without --gz: the plain encode, then a 16-thread zlib level-1 BGZF writer over the tar; 16 threads of
            zlib over the BGZF members into a file in --dir, then the plain decode.
-One JSON line.
+--level: the compressor level of --gz and of the kernel step (`--bgzf-level`).  One JSON line.
 """
 import argparse
 import json
@@ -96,14 +96,15 @@ def kernel(args):
     # both sides into one preallocated output, through the library's entries: only the device work and its host round trips are timed
     import ctypes as C
     from uq_amd._lib import call
-    blob, sizes = ops.bgzf_compress_parts(ctx, parts)
+    blob, sizes = ops.bgzf_compress_parts(ctx, parts, level=args.level)
+    flags = ops.bgzf_level_flags(args.level)
     arr, keep = ops._bgzf_parts_arg(parts)
     out = torch.empty(ops.bgzf_parts_bound(parts), dtype=torch.uint8, device=ctx.device)
     ps, nout = (C.c_uint64 * len(parts))(), C.c_uint64()
     ptr = lambda t_: C.c_void_p(t_.data_ptr())
 
     def by_parts():
-        call('uq_bgzf_compress_parts', ctx.h, arr, len(parts), ptr(out), out.numel(), ps, C.byref(nout), 0)
+        call('uq_bgzf_compress_parts', ctx.h, arr, len(parts), ptr(out), out.numel(), ps, C.byref(nout), flags)
     by_parts()
     same = nout.value == blob.numel() and torch.equal(out[:nout.value], blob)
     # what it replaces: per member, a device-side header || payload copy, then uq_bgzf_compress on it (headers uploaded beforehand)
@@ -116,7 +117,7 @@ def kernel(args):
             n = len(h) + d.numel()
             if dh is not None: cat[:len(h)].copy_(dh)
             cat[len(h):n].copy_(d)
-            call('uq_bgzf_compress', ctx.h, ptr(cat), n, ptr(out[total:]), out.numel() - total, C.byref(nout), 0)
+            call('uq_bgzf_compress', ctx.h, ptr(cat), n, ptr(out[total:]), out.numel() - total, C.byref(nout), flags)
             total += nout.value
         return total
     same = same and per_member() == blob.numel() and torch.equal(out[:blob.numel()], blob)
@@ -153,7 +154,7 @@ def kernel(args):
                                  'parts_ms_events': round(parts_ms, 3), 'per_member_copy_and_compress_ms_events': round(member_ms, 3),
                                  'parts_over_per_member': round(parts_ms / member_ms, 4), 'same_bytes': bool(same),
                                  'inflate_members_ms_events': round(inflate_ms, 3), 'gz_members': len(m),
-                                 'device_inflate_equals_tar_members': bool(ok), 'reps': args.reps}}))
+                                 'device_inflate_equals_tar_members': bool(ok), 'reps': args.reps, 'level': args.level}}))
 
 
 def bgzf_write(src, dst):
@@ -211,13 +212,14 @@ def main():
     ap.add_argument('--dir', default='/dev/shm')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--skip-gzip6', action='store_true')
+    ap.add_argument('--level', type=int, choices=[1, 2], default=1)
     ap.add_argument('--make', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--kernel', help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.make: return make(args)
     if args.kernel: return kernel(args)
     me = [sys.executable, os.path.abspath(__file__), '--reads', str(args.reads), '--binned-reads', str(args.binned_reads), '--length',
-          str(args.length), '--dir', args.dir, '--reps', str(args.reps)]
+          str(args.length), '--dir', args.dir, '--reps', str(args.reps), '--level', str(args.level)]
     env = dict(os.environ, UQ_TIMING='1', PYTHONPATH=HERE)
     result = last_json(child(me + ['--make'], 300).stdout, 'make')
 
@@ -234,7 +236,7 @@ def main():
             made += [p(e) for e in ('.fastq', '.uQ', '.uQ.gz', '.gzip6.uQ.gz', '.host.uQ.gz', '.host.uQ', '.out.fastq')]
             r = {}
             r['encode_plain_work_s'] = cli(['-i', p('.fastq'), '-o', p('.uQ')] + RAW)
-            r['encode_gz_work_s'] = cli(['-i', p('.fastq'), '-o', p('.uQ.gz'), '--gz'] + RAW)
+            r['encode_gz_work_s'] = cli(['-i', p('.fastq'), '-o', p('.uQ.gz'), '--gz', '--bgzf-level', str(args.level)] + RAW)
             r.update(last_json(child(me + ['--kernel', p('.uQ')], 600).stdout, 'kernel')['kernel'])
             # the decoder writes to stdout: into a file in --dir
             def decode(src):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BGZF output: the device deflate (uq_bgzf_compress) against zlib on the host, on bench.py's workload.
 
-    python tools/bench_deflate.py [--reads 10000000] [--dir /dev/shm] [--reps 10] [--rocprof]
+    python tools/bench_deflate.py [--reads 10000000] [--dir /dev/shm] [--reps 10] [--rocprof] [--level {1,2}]
 
 bench.py's reads (synth-v1, seed 20261005, 150 bp) are written as plain FASTQ and encoded to a .uQ container.  Then, each GPU step in a
 child process under its own time limit, stopping at the first failure:
@@ -11,7 +11,8 @@ child process under its own time limit, stopping at the first failure:
   cli      `python -m uq_amd.uq --decode` with UQ_TIMING=1: work_s of the plain decode, of `--decode --bgzf`, and of `--decode` piped into a
            16-thread zlib level-1 BGZF writer (the host baseline; its wall time too);
   rocprof  (--rocprof) the kernel step once more under `rocprofv3 --kernel-trace --stats`: the kernel's own time.
-One JSON line.  Synthetic reads compress unlike real ones (random bases and qualities): the ratios here are not a real file's.
+--level: the compressor level of the kernel and CLI steps (`--bgzf-level`); the host baseline's zlib level is --host-level (1; DESIGN.md
+section 18 compares level 2 with zlib level 6).  One JSON line.  Synthetic reads compress unlike real ones (random bases and qualities): the ratios here are not a real file's.
 """
 import argparse
 import glob
@@ -74,12 +75,12 @@ def kernel(args):
     from uq_amd.hostio import Staging
     ctx = Context(0)
     d_text = Staging(ctx).file_to_device(args.kernel)
-    blob = ops.bgzf_compress(ctx, d_text)
+    blob = ops.bgzf_compress(ctx, d_text, level=args.level)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ops.bgzf_compress(ctx, d_text)
+    ops.bgzf_compress(ctx, d_text, level=args.level)
     e0.record()
     for _ in range(args.reps):
-        ops.bgzf_compress(ctx, d_text)
+        ops.bgzf_compress(ctx, d_text, level=args.level)
     e1.record()
     e1.synchronize()
     ms = e0.elapsed_time(e1) / args.reps
@@ -88,18 +89,18 @@ def kernel(args):
     ok = kind == ops.GZIP_BGZF and bad is None and torch.equal(out, d_text)
     print(json.dumps({'kernel': {'in_bytes': d_text.numel(), 'out_bytes': blob.numel(), 'ratio': round(d_text.numel() / blob.numel(), 4),
                                  'members': len(members), 'compress_ms_events': round(ms, 3), 'compress_in_GBps': round(d_text.numel() / ms / 1e6, 2),
-                                 'reps': args.reps, 'device_inflate_equals_plain_decode': bool(ok)}}))
+                                 'reps': args.reps, 'level': args.level, 'device_inflate_equals_plain_decode': bool(ok)}}))
 
 
 def writer(args):
-    """Host baseline: stdin -> BGZF level 1 on 16 threads -> file."""
+    """Host baseline: stdin -> BGZF at zlib level --host-level on 16 threads -> file."""
     with open(args.bgzf_writer, 'wb') as f, ThreadPoolExecutor(16) as pool:
         inp = sys.stdin.buffer
         while True:
             buf = inp.read(CHUNK * 256)
             if not buf: break
             mv = memoryview(buf)
-            for m in pool.map(lambda i: bgzf_member(mv[i:i + CHUNK], 1), range(0, len(buf), CHUNK)):
+            for m in pool.map(lambda i: bgzf_member(mv[i:i + CHUNK], args.host_level), range(0, len(buf), CHUNK)):
                 f.write(m)
         f.write(EOF)
 
@@ -127,6 +128,8 @@ def main():
     ap.add_argument('--dir', default='/dev/shm')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--rocprof', action='store_true')
+    ap.add_argument('--level', type=int, choices=[1, 2], default=1)
+    ap.add_argument('--host-level', type=int, default=1)
     ap.add_argument('--make', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--kernel', help=argparse.SUPPRESS)
     ap.add_argument('--bgzf-writer', help=argparse.SUPPRESS)
@@ -137,8 +140,8 @@ def main():
 
     work = os.path.join(args.dir, 'uq_bench_deflate_%d' % os.getpid())
     os.makedirs(work)
-    me = [sys.executable, os.path.abspath(__file__), '--reads', str(args.reads), '--length', str(args.length), '--dir', work]
-    res = {'bench': 'deflate', 'workload': '%d x %d bp synth-v1 (seed %d), BGZF members of %d bytes; synthetic reads compress unlike real ones'
+    me = [sys.executable, os.path.abspath(__file__), '--reads', str(args.reads), '--length', str(args.length), '--dir', work, '--level', str(args.level), '--host-level', str(args.host_level)]
+    res = {'bench': 'deflate', 'level': args.level, 'host_zlib_level': args.host_level, 'workload': '%d x %d bp synth-v1 (seed %d), BGZF members of %d bytes; synthetic reads compress unlike real ones'
            % (args.reads, args.length, SEED, CHUNK)}
     try:
         m = last_json(child(me + ['--make'], 900).stdout, '"make"')
@@ -150,9 +153,9 @@ def main():
         py = sys.executable
         plain = os.path.join(work, 'decoded.fastq')
         runs = {'decode': '%s -m uq_amd.uq -i %s --decode --quiet > %s' % (py, uq_file, plain),
-                'decode_bgzf': '%s -m uq_amd.uq -i %s --decode --bgzf --quiet > %s' % (py, uq_file, os.path.join(work, 'gpu.fastq.gz')),
-                'decode_host_zlib1_16t': '%s -m uq_amd.uq -i %s --decode --quiet | %s %s --bgzf-writer %s' % (
-                    py, uq_file, py, os.path.abspath(__file__), os.path.join(work, 'host.fastq.gz'))}
+                'decode_bgzf': '%s -m uq_amd.uq -i %s --decode --bgzf --bgzf-level %d --quiet > %s' % (py, uq_file, args.level, os.path.join(work, 'gpu.fastq.gz')),
+                'decode_host_zlib1_16t': '%s -m uq_amd.uq -i %s --decode --quiet | %s %s --host-level %d --bgzf-writer %s' % (
+                    py, uq_file, py, os.path.abspath(__file__), args.host_level, os.path.join(work, 'host.fastq.gz'))}
         for name, cmd in runs.items():
             t0 = time.perf_counter()
             r = child(cmd, 900, env, shell=True)

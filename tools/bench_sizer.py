@@ -2,10 +2,10 @@
 """The --test sizer: uq_deflate_size against uq_bgzf_compress on the candidates of bench.py's workload, the CLI's `--test` with the device
 sizer against a host compressor, and (on the CPU) whether the sizer ranks the layouts as stock compressors do.
 
-    python tools/bench_sizer.py kernel   [--reads 10000000] [--reps 5] [--compress-lib PATH]
+    python tools/bench_sizer.py kernel   [--reads 10000000] [--reps 5] [--compress-lib PATH] [--level {1,2}]
     python tools/bench_sizer.py cli      [--reads 1000000] [--dir /dev/shm] [--host-compressor "gzip -1"]
     python tools/bench_sizer.py grid     [--reads 10000000] [--dir /dev/shm]
-    python tools/bench_sizer.py ordering [--reads 100000]                (no GPU)
+    python tools/bench_sizer.py ordering [--reads 100000] [--level {1,2}] (no GPU)
 
 kernel    bench.py's reads (synth-v1, seed 20261005, 150 bp) packed on the device; for the DNA and the QUAL table and each of the eight
           layouts: uq_pattern into one buffer, then uq_deflate_size (header + payload) and uq_bgzf_compress (payload) over --reps warm
@@ -17,7 +17,7 @@ cli       `python -m uq_amd.uq --test --sort None --raw DNA QUAL QNAME` (one mix
 grid      the full 32-mix grid with --device-compressor: work_s.
 ordering  synthetic reads of both geometries (150 bp fixed, 36-301 bp): S of the 16 candidates of the no-sort all-raw mix next to
           len(zlib.compress(B, 6)) and len(lzma.compress(B)) of the same bytes, and the three orderings.  Host code only.
-Every GPU step runs in a child process under its own time limit, and the tool stops at the first failure.  One JSON line per step.
+--level: the compressor level of every step (`--bgzf-level`).  Every GPU step runs in a child process under its own time limit, and the tool stops at the first failure.  One JSON line per step.
 """
 import argparse
 import json
@@ -61,11 +61,11 @@ def kernel_child(a):
                 for what in (('compress',) if a.compress_only else ('size', 'compress')):
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     if what == 'size':
-                        q = ops.DeflateSizes(ctx, 1)
+                        q = ops.DeflateSizes(ctx, 1, level=a.level)
                         e0.record(); q.add(header, payload); e1.record()
                         row['S'] = q.fetch()[0]
                     else:
-                        e0.record(); out = ops.bgzf_compress(ctx, payload, eof=False); e1.record()
+                        e0.record(); out = ops.bgzf_compress(ctx, payload, eof=False, level=a.level); e1.record()
                         row['compressed_bytes'] = out.numel()
                         del out
                     torch.cuda.synchronize()
@@ -76,7 +76,7 @@ def kernel_child(a):
                     row[what + '_GBps'] = round(rows * cols / min(ts) / 1e9, 2)
             if times['size']: row['size_over_compress'] = round(min(times['compress']) / min(times['size']), 3)
             rows_out.append(row)
-    print(json.dumps({'kernel': rows_out, 'lib': os.environ.get('UQ_LIB_PATH') or 'this build', 'reads': a.reads}), flush=True)
+    print(json.dumps({'kernel': rows_out, 'lib': os.environ.get('UQ_LIB_PATH') or 'this build', 'reads': a.reads, 'level': a.level}), flush=True)
 
 
 def _child(argv, limit, env=None):
@@ -89,7 +89,7 @@ def _child(argv, limit, env=None):
 
 
 def kernel(a):
-    me = [os.path.abspath(__file__), 'kernel', '--child', '--reads', str(a.reads), '--reps', str(a.reps), '--length', str(a.length)]
+    me = [os.path.abspath(__file__), 'kernel', '--child', '--reads', str(a.reads), '--reps', str(a.reps), '--length', str(a.length), '--level', str(a.level)]
     print(_child(me, a.limit).stdout.strip())
     if a.compress_lib:
         print(_child(me + ['--compress-only'], a.limit, {'UQ_LIB_PATH': os.path.abspath(a.compress_lib)}).stdout.strip())
@@ -106,7 +106,7 @@ def _write_reads(a):
 
 def _uq(a, path, flags, limit):
     t0 = time.perf_counter()
-    r = _child(['-m', 'uq_amd.uq', '-i', path, '-o', path + '.uQ', '--test'] + flags, limit, {'UQ_TIMING': '1', 'PYTHONPATH': HERE})
+    r = _child(['-m', 'uq_amd.uq', '-i', path, '-o', path + '.uQ', '--test'] + flags + (['--bgzf-level', str(a.level)] if '--device-compressor' in flags and a.level != 1 else []), limit, {'UQ_TIMING': '1', 'PYTHONPATH': HERE})
     timing = [json.loads(l) for l in r.stderr.split('\n') if l.startswith('{"uq_timing"')]
     best = [l.strip() for l in r.stdout.split('\n') if l.strip().startswith('--')]
     return {'flags': flags, 'work_s': timing[-1]['work_s'], 'wall_s': round(time.perf_counter() - t0, 2), 'best': best[-1] if best else None}
@@ -155,11 +155,11 @@ def ordering(a):
             for pat in uq.PATTERNS:
                 r = np.rot90(T, int(pat[0]))
                 B = uq.pattern_header(T.shape[0], T.shape[1], pat) + (np.ascontiguousarray(r) if pat.endswith('.1') else np.asfortranarray(r)).tobytes(order='A')
-                rows_out.append({'table': name, 'pattern': pat, 'bytes': len(B), 'S': ops.deflate_size_host(B), 'zlib6': len(zlib.compress(B, 6)),
+                rows_out.append({'table': name, 'pattern': pat, 'bytes': len(B), 'S': ops.deflate_size_host(B, level=a.level), 'zlib6': len(zlib.compress(B, 6)),
                                  'lzma': len(lzma.compress(B))})
         order = {name: {k: [r['pattern'] for r in sorted((r for r in rows_out if r['table'] == name), key=lambda r: (r[k], r['pattern']))]
                         for k in ('S', 'zlib6', 'lzma')} for name in ('DNA', 'QUAL')}
-        print(json.dumps({'ordering': label, 'reads': a.reads, 'candidates': rows_out, 'order': order}), flush=True)
+        print(json.dumps({'ordering': label, 'reads': a.reads, 'level': a.level, 'candidates': rows_out, 'order': order}), flush=True)
 
 
 def main():
@@ -172,6 +172,7 @@ def main():
     ap.add_argument('--limit', type=int, default=900, help='seconds a child step may take')
     ap.add_argument('--host-compressor', default='gzip -1')
     ap.add_argument('--compress-lib', help='kernel: also time uq_bgzf_compress from this build of libuqhip.so')
+    ap.add_argument('--level', type=int, choices=[1, 2], default=1, help='the compressor level (--bgzf-level)')
     ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--compress-only', action='store_true', help=argparse.SUPPRESS)
     a = ap.parse_args()

@@ -174,8 +174,11 @@ SIGNATURES = {
     'uq_bgzf_compress_parts': [_vp, _P(BgzfPart), _u32, _vp, _u64, _P(_u64), _P(_u64), _u32],
     'uq_bgzf_parts_bound': [_P(BgzfPart), _u32, _P(_u64)],
     'uq_bgzf_compress_block_host': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32)],
+    'uq_bgzf_compress_block_host_l': [_vp, _u64, _vp, _u64, _P(_u64), _P(_u32), _u32],
     'uq_deflate_size': [_vp, _vp, _u32, _vp, _u64, _vp, _vp],
     'uq_deflate_size_host': [_vp, _u32, _vp, _u64, _P(_u64)],
+    'uq_deflate_size_l': [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32],
+    'uq_deflate_size_host_l': [_vp, _u32, _vp, _u64, _P(_u64), _u32],
 }
 
 _lib = None

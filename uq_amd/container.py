@@ -280,9 +280,9 @@ def member_aligned_layout(frame_sizes, part_sizes):
     return layout
 
 
-def member_aligned_host(tar_bytes):
-    """The member-aligned BGZF of an existing plain tar, built on the host with the device compressor's code (the host twin of the --gz
-    writer).  Returns (bytes, layout, names)."""
+def member_aligned_host(tar_bytes, level=1):
+    """The member-aligned BGZF of an existing plain tar, built on the host with the device compressor's code at that level (the host twin
+    of the --gz writer).  Returns (bytes, layout, names)."""
     from . import ops
 
     class Host:
@@ -294,11 +294,11 @@ def member_aligned_host(tar_bytes):
     out, frames, parts, pos = [], [], [], 0
     for name in order + [None]:
         end = members[name][0] if name else len(tar_bytes)
-        piece = ops.bgzf_block_host(tar_bytes[pos:end])
+        piece = ops.bgzf_block_host(tar_bytes[pos:end], level=level)
         out.append(piece); frames.append(len(piece))
         if name is None: break
         offset, size = members[name]
-        blob, sizes = ops.bgzf_compress_parts_host([(b'', tar_bytes[offset:offset + size])])
+        blob, sizes = ops.bgzf_compress_parts_host([(b'', tar_bytes[offset:offset + size])], level=level)
         out.append(blob); parts.append(sizes[0])
         pos = offset + size
     out.append(ops.BGZF_EOF)

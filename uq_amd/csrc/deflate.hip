@@ -11,7 +11,8 @@
 // across the buffers, the block cuts restarting at every buffer.
 //
 // LDS: UqDeflateLds is about 151 KiB (the block, one match-length byte per position, the head table / parse window / Huffman scratch, the
-// code tables): one workgroup of UQ_DEF_THREADS threads per CU.
+// code tables): one workgroup of UQ_DEF_THREADS threads per CU.  Level 2 (UQ_BGZF_LEVEL2: UqDeflateLds2) adds 1 KiB; the workspace and
+// everything around the compressor are the same for both levels.
 #include "inflate_env.h"
 #include "deflate_core.h"
 #include <vector>
@@ -36,10 +37,14 @@ struct DevEnv {
     __device__ void word_or(uint32_t w, uint32_t v) { atomicOr(out + w, v); }
 };
 
+template <int kLevel> struct LdsOf { typedef UqDeflateLds type; };
+template <> struct LdsOf<2> { typedef UqDeflateLds2 type; };
+
+template <int kLevel>
 __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_kernel(const uint8_t* __restrict__ in, uint64_t nbytes, uint64_t first_block,
                                                                       uint8_t* __restrict__ slots, uint16_t* __restrict__ dist,
                                                                       uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2n x2n) {
-    __shared__ __attribute__((aligned(16))) UqDeflateLds s;
+    __shared__ __attribute__((aligned(16))) typename LdsOf<kLevel>::type s;
     __shared__ uint32_t x2n_s[32];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
     const uint64_t off = (first_block + b) * (uint64_t)UQ_DEF_MAX_IN;
@@ -56,7 +61,7 @@ __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_kernel(const uint
     __syncthreads();
     DevEnv env{(uint32_t*)(slots + (uint64_t)b * UQ_DEF_SLOT), dist + (uint64_t)b * UQ_DEF_MAX_IN, x2n_s};
     uint32_t mb = 0;
-    const int st = uq_deflate_block(env, &s, n, UQ_DEF_SLOT, tid, UQ_DEF_THREADS, &mb);
+    const int st = uq_deflate_block_l<kLevel>(env, &s, n, UQ_DEF_SLOT, tid, UQ_DEF_THREADS, &mb);
     if (tid == 0) { sizes[b] = st == UQ_DEF_OK ? mb : 0; status[b] = (uint32_t)st; }
 }
 
@@ -105,11 +110,12 @@ template <int WS> __device__ __forceinline__ Vec4 shifted_vec(Vec4 a, Vec4 c, ui
 // (block 0 of a part only: a prefix is at most 256 bytes), in[lo, n) from the part's buffer.  The LDS side is written in whole 16-byte
 // vectors whatever the source's alignment: a source that is not 16-byte aligned is read as the two aligned 16-byte vectors that cover
 // the wanted one (each holds at least one byte of it, so no read leaves the buffer's 16-byte granules) and shifted into place.
+template <int kLevel>
 __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_parts_kernel(const PartBlock* __restrict__ table, const PartSrc* __restrict__ parts,
                                                                             const uint8_t* __restrict__ arena, uint64_t first_block,
                                                                             uint8_t* __restrict__ slots, uint16_t* __restrict__ dist,
                                                                             uint32_t* __restrict__ sizes, uint32_t* __restrict__ status, X2n x2n) {
-    __shared__ __attribute__((aligned(16))) UqDeflateLds s;
+    __shared__ __attribute__((aligned(16))) typename LdsOf<kLevel>::type s;
     __shared__ uint32_t x2n_s[32];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
     const PartBlock e = table[first_block + b];
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(UQ_DEF_THREADS) void bgzf_deflate_parts_kernel(cons
     __syncthreads();
     DevEnv env{(uint32_t*)(slots + (uint64_t)b * UQ_DEF_SLOT), dist + (uint64_t)b * UQ_DEF_MAX_IN, x2n_s};
     uint32_t mb = 0;
-    const int st = e.n > UQ_DEF_MAX_IN ? (int)UQ_DEF_TOO_LARGE : uq_deflate_block(env, &s, n, UQ_DEF_SLOT, tid, UQ_DEF_THREADS, &mb);
+    const int st = e.n > UQ_DEF_MAX_IN ? (int)UQ_DEF_TOO_LARGE : uq_deflate_block_l<kLevel>(env, &s, n, UQ_DEF_SLOT, tid, UQ_DEF_THREADS, &mb);
     if (tid == 0) { sizes[b] = st == UQ_DEF_OK ? mb : 0; status[b] = (uint32_t)st; }
 }
 
@@ -198,7 +204,7 @@ extern "C" int uq_bgzf_compress(uq_ctx* c, const uint8_t* d_in, uint64_t nbytes,
                                 uint32_t flags) {
     UQ_REQUIRE(c && h_out_bytes, "uq_bgzf_compress: null argument");
     UQ_REQUIRE((d_in || !nbytes) && (d_out || !out_capacity), "uq_bgzf_compress: null buffer");
-    UQ_REQUIRE(!(flags & ~(uint32_t)UQ_BGZF_EOF), "uq_bgzf_compress: unknown flags 0x%x", flags);
+    UQ_REQUIRE(!(flags & ~(uint32_t)(UQ_BGZF_EOF | UQ_BGZF_LEVEL2)), "uq_bgzf_compress: unknown flags 0x%x", flags);
     *h_out_bytes = 0;
     const uint64_t nblocks = (nbytes + UQ_DEF_MAX_IN - 1) / UQ_DEF_MAX_IN;
     const uint32_t chunk = (uint32_t)(nblocks < UQ_DEF_CHUNK ? nblocks : UQ_DEF_CHUNK);
@@ -223,7 +229,8 @@ extern "C" int uq_bgzf_compress(uq_ctx* c, const uint8_t* d_in, uint64_t nbytes,
             const uint32_t nb = (uint32_t)(nblocks - b0 < chunk ? nblocks - b0 : chunk);
             hipError_t e = hipMemsetAsync(slots, 0, (size_t)nb * UQ_DEF_SLOT, c->stream);
             if (e == hipSuccess) {
-                bgzf_deflate_kernel<<<nb, UQ_DEF_THREADS, 0, c->stream>>>(d_in, nbytes, b0, slots, dist, sizes, status, x2n);
+                if (flags & UQ_BGZF_LEVEL2) bgzf_deflate_kernel<2><<<nb, UQ_DEF_THREADS, 0, c->stream>>>(d_in, nbytes, b0, slots, dist, sizes, status, x2n);
+                else bgzf_deflate_kernel<1><<<nb, UQ_DEF_THREADS, 0, c->stream>>>(d_in, nbytes, b0, slots, dist, sizes, status, x2n);
                 e = hipGetLastError();
             }
             const int r = e == hipSuccess ? uq_scan_exclusive_u32(c, sizes, offs, nb, total) : 0;
@@ -291,7 +298,7 @@ extern "C" int uq_bgzf_compress_parts(uq_ctx* c, const uq_bgzf_part* h_parts, ui
                                       uint64_t* h_part_bytes, uint64_t* h_out_bytes, uint32_t flags) {
     UQ_REQUIRE(c && h_out_bytes && (h_part_bytes || !nparts), "uq_bgzf_compress_parts: null argument");
     UQ_REQUIRE(d_out || !out_capacity, "uq_bgzf_compress_parts: null buffer");
-    UQ_REQUIRE(!(flags & ~(uint32_t)UQ_BGZF_EOF), "uq_bgzf_compress_parts: unknown flags 0x%x", flags);
+    UQ_REQUIRE(!(flags & ~(uint32_t)(UQ_BGZF_EOF | UQ_BGZF_LEVEL2)), "uq_bgzf_compress_parts: unknown flags 0x%x", flags);
     *h_out_bytes = 0;
     uint64_t nblocks = 0;
     UQ_TRY(parts_check(h_parts, nparts, "uq_bgzf_compress_parts", &nblocks));
@@ -340,7 +347,9 @@ extern "C" int uq_bgzf_compress_parts(uq_ctx* c, const uq_bgzf_part* h_parts, ui
         for (uint64_t b0 = 0; b0 < nblocks; b0 += chunk) {
             const uint32_t nb = (uint32_t)(nblocks - b0 < chunk ? nblocks - b0 : chunk);
             UQ_CHECK_HIP(hipMemsetAsync(slots, 0, (size_t)nb * UQ_DEF_SLOT, c->stream));
-            bgzf_deflate_parts_kernel<<<nb, UQ_DEF_THREADS, 0, c->stream>>>(table, src, arena, b0, slots, dist, sizes, status, x2n);
+            if (flags & UQ_BGZF_LEVEL2)
+                bgzf_deflate_parts_kernel<2><<<nb, UQ_DEF_THREADS, 0, c->stream>>>(table, src, arena, b0, slots, dist, sizes, status, x2n);
+            else bgzf_deflate_parts_kernel<1><<<nb, UQ_DEF_THREADS, 0, c->stream>>>(table, src, arena, b0, slots, dist, sizes, status, x2n);
             UQ_LAUNCH_CHECK();
             UQ_TRY(uq_scan_exclusive_u32(c, sizes, offs, nb, total));
             uint64_t h_total = 0;
@@ -373,12 +382,11 @@ extern "C" int uq_bgzf_compress_parts(uq_ctx* c, const uq_bgzf_part* h_parts, ui
     return 0;
 }
 
-extern "C" int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
-                                           uint32_t* h_status) {
-    UQ_REQUIRE(h_out_bytes && h_status && (h_in || !nbytes) && (h_out || !capacity), "uq_bgzf_compress_block_host: null argument");
+template <int kLevel>
+static int block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes, uint32_t* h_status) {
     *h_out_bytes = 0;
     if (nbytes > UQ_DEF_MAX_IN) { *h_status = UQ_DEF_TOO_LARGE; return 0; }
-    UqDeflateLds* s = new UqDeflateLds();
+    typename LdsOf<kLevel>::type* s = new typename LdsOf<kLevel>::type();
     uint16_t* dist = new uint16_t[UQ_DEF_MAX_IN];
     uint32_t x2n[32];
     uq_crc_x2n_init(x2n);
@@ -387,10 +395,24 @@ extern "C" int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes,
     if (cap) memset(h_out, 0, cap);
     HostEnv env{h_out, cap, dist, x2n};
     uint32_t mb = 0;
-    const int st = uq_deflate_block(env, s, (uint32_t)nbytes, cap, 0, 1, &mb);
+    const int st = uq_deflate_block_l<kLevel>(env, s, (uint32_t)nbytes, cap, 0, 1, &mb);
     delete[] dist;
     delete s;
     *h_status = (uint32_t)st;
     *h_out_bytes = mb;
     return 0;
+}
+
+extern "C" int uq_bgzf_compress_block_host(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
+                                           uint32_t* h_status) {
+    UQ_REQUIRE(h_out_bytes && h_status && (h_in || !nbytes) && (h_out || !capacity), "uq_bgzf_compress_block_host: null argument");
+    return block_host<1>(h_in, nbytes, h_out, capacity, h_out_bytes, h_status);
+}
+
+extern "C" int uq_bgzf_compress_block_host_l(const uint8_t* h_in, uint64_t nbytes, uint8_t* h_out, uint64_t capacity, uint64_t* h_out_bytes,
+                                             uint32_t* h_status, uint32_t flags) {
+    UQ_REQUIRE(h_out_bytes && h_status && (h_in || !nbytes) && (h_out || !capacity), "uq_bgzf_compress_block_host_l: null argument");
+    UQ_REQUIRE(!(flags & ~(uint32_t)UQ_BGZF_LEVEL2), "uq_bgzf_compress_block_host_l: unknown flags 0x%x", flags);
+    return flags & UQ_BGZF_LEVEL2 ? block_host<2>(h_in, nbytes, h_out, capacity, h_out_bytes, h_status)
+                                  : block_host<1>(h_in, nbytes, h_out, capacity, h_out_bytes, h_status);
 }

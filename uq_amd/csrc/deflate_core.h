@@ -19,6 +19,16 @@
 //   6. Walk 3: every range of bits (the staged header, each sub-segment, the end-of-block code and the trailer) is written by one thread:
 //      words it covers whole are stored, the partial words at its ends are OR-ed in (the output starts zeroed, and OR is commutative).
 //
+// Level 2 (kLevel = 2: UqDeflateLds2 / UqDeflateSizeLds2, uq_deflate_block_l / uq_deflate_block_size_l) changes phases 2 and 3 only:
+//   2. Up to five candidates per position, the longest wins, a tie takes the nearer: the two positions of a packed `head` word
+//      ((newest + 1) << 16 | (older + 1): after a round, atomic max with ((p + 1) << 16) | the newest from before the round, which every
+//      position noted in `prev` before the barrier), the fixed distances 1 and 2 (runs, from the block's first bytes on), and the
+//      distance of the last match of the round before (`rep`, an atomic max of (position << 16 | distance - 1): a copy longer than a
+//      round goes on where the hash table has long been overwritten).
+//   3. Lazy parse: a position is a literal when it has no match, or when its match is shorter than UQ_DEF_LAZY_MAX and the match at the
+//      next position is longer.  The decision reads len[p] and len[p + 1] only (uq_def_tok), so the pointer jumping and the three walks
+//      keep their shape.
+//
 // Safety: reads of the block stay below n (n <= UQ_DEF_MAX_IN); the member's size is known before anything is written and is checked
 // against the capacity (UQ_DEF_NO_SPACE otherwise); every loop has a bound that does not depend on the data.
 #pragma once
@@ -46,6 +56,7 @@ enum {
 #define UQ_DEF_WIN 8192u           // positions of a pointer-jumping window (u16 entries in the head table's space)
 #define UQ_DEF_HDR_WORDS 160       // gzip header + dynamic block header: 144 + 17 + 57 + 316 * 14 bits < 160 words
 #define UQ_DEF_NONE 0xFFFFu
+#define UQ_DEF_LAZY_MAX 32u        // level 2: a match of at least this many bytes is taken without looking at the next position
 
 struct UqDefHuffScratch {
     uint16_t sorted[288];          // symbols with a weight, by (weight, symbol)
@@ -92,6 +103,17 @@ struct UqDeflateSizeLds {
     uint32_t nrle, hlit, hdist, hclen, hdr_bits, member_bytes, stored, body_bits;
 };
 
+// level 2: the level-1 state, the pre-round newest position (+ 1) of every position of the round, and the last match of a round
+// (((position in the round + 1) << 16) | (distance - 1); 0 = none): one word read, the other written, swapped every round
+struct UqDeflateLds2 : UqDeflateLds {
+    uint16_t prev[UQ_DEF_ROUND];
+    uint32_t rep[2];
+};
+struct UqDeflateSizeLds2 : UqDeflateSizeLds {
+    uint16_t prev[UQ_DEF_ROUND];
+    uint32_t rep[2];
+};
+
 UQ_DEF_HD uint32_t uq_def_log2(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
 
 // the length of a len[] code, and the code of a length
@@ -124,6 +146,24 @@ UQ_DEF_HD uint32_t uq_def_dextra(uint32_t sym) { return sym < 4 ? 0u : (sym >> 1
 UQ_DEF_HD uint32_t uq_def_hash(const uint8_t* p) {
     const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     return (v * 2654435761u) >> (32 - UQ_DEF_HASH_BITS);
+}
+
+// the bytes (at most lim) that in[c...] and in[p...] share, c < p
+UQ_DEF_HD uint32_t uq_def_common(const uint8_t* in, uint32_t c, uint32_t p, uint32_t lim) {
+    uint32_t L = 0;
+    while (L < lim && in[c + L] == in[p + L]) ++L;
+    return L;
+}
+
+// the token at p as the parse takes it: 0 = a literal, else the len[] code of its match.  Level 2 is lazy: a match shorter than
+// UQ_DEF_LAZY_MAX gives way to a longer one at p + 1 (len[] codes order as lengths do).
+template <int kLevel>
+UQ_DEF_HD uint32_t uq_def_tok(const uint8_t* len, uint32_t p, uint32_t n) {
+    const uint32_t v = len[p];
+    if constexpr (kLevel >= 2) {
+        if (v && v < UQ_DEF_LAZY_MAX - 2 && p + 1 < n && len[p + 1] > v) return 0;
+    }
+    return v;
 }
 
 // A range of the member's bits [b0, b1) written word by word through Env: whole words stored, the partial words at either end OR-ed.
@@ -225,7 +265,7 @@ UQ_DEF_HD void uq_def_codes(const uint8_t* lens, uint32_t n, uint16_t* codes) {
 // first bit.  Without it (Lds = UqDeflateSizeLds) the same matches, parse, histograms and code lengths are computed and nothing else: the
 // distance workspace holds distance symbols (one byte per position will do: Env::dist_put / dist_get take and give the symbol), and the
 // bits of the tokens are counted from the histograms (sum of frequency x (code length + extra bits)) instead of by a second walk.
-template <bool kEmit, class Env, class Lds>
+template <bool kEmit, int kLevel = 1, class Env, class Lds>
 UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t nth) {
     if constexpr (kEmit)
         for (uint32_t e = tid; e < 256; e += nth) s->crctab[e] = uq_crc_table_entry(e);
@@ -235,6 +275,7 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
     for (uint32_t e = tid; e < 20; e += nth) s->cfreq[e] = 0;
     for (uint32_t e = tid; e < 16; e += nth) s->in[n + e] = 0;
     if constexpr (kEmit) { if (tid == 0) s->crc0 = 0; } else { if (tid == 0) s->body_bits = 0; }
+    if constexpr (kLevel >= 2) { if (tid == 0) { s->rep[0] = 0; s->rep[1] = 0; } }
     env.sync();
 
     // ---- 1. CRC-32
@@ -249,36 +290,73 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
     const uint32_t nrounds = (n + UQ_DEF_ROUND - 1) / UQ_DEF_ROUND;
     for (uint32_t r = 0; r < nrounds; ++r) {
         const uint32_t r0 = r * UQ_DEF_ROUND, r1 = r0 + UQ_DEF_ROUND < n ? r0 + UQ_DEF_ROUND : n;
-        for (uint32_t p = r0 + tid; p < r1; p += nth) {
-            uint32_t v = 0;
-            if (p + 4 <= n) {
-                const uint32_t c1 = s->u.head[uq_def_hash(s->in + p)];
-                if (c1 && p - (c1 - 1) <= 32768u) {
-                    const uint32_t c = c1 - 1, lim = n - p < 258 ? n - p : 258;
-                    uint32_t L = 0;
-                    while (L < lim && s->in[c + L] == s->in[p + L]) ++L;
-                    if (L >= 3 && !(L == 3 && p - c > 4096)) {
-                        v = uq_def_lcode(L);
-                        if constexpr (kEmit) env.dist_put(p, p - c);
-                        else { uint32_t dv, dn; env.dist_put(p, uq_def_dsym(p - c, dv, dn)); }
+        if constexpr (kLevel == 1) {
+            for (uint32_t p = r0 + tid; p < r1; p += nth) {
+                uint32_t v = 0;
+                if (p + 4 <= n) {
+                    const uint32_t c1 = s->u.head[uq_def_hash(s->in + p)];
+                    if (c1 && p - (c1 - 1) <= 32768u) {
+                        const uint32_t c = c1 - 1, lim = n - p < 258 ? n - p : 258;
+                        uint32_t L = 0;
+                        while (L < lim && s->in[c + L] == s->in[p + L]) ++L;
+                        if (L >= 3 && !(L == 3 && p - c > 4096)) {
+                            v = uq_def_lcode(L);
+                            if constexpr (kEmit) env.dist_put(p, p - c);
+                            else { uint32_t dv, dn; env.dist_put(p, uq_def_dsym(p - c, dv, dn)); }
+                        }
                     }
                 }
+                s->len[p] = (uint8_t)v;
             }
-            s->len[p] = (uint8_t)v;
+            env.sync();
+            for (uint32_t p = r0 + tid; p < r1; p += nth)
+                if (p + 4 <= n) env.lds_max(&s->u.head[uq_def_hash(s->in + p)], p + 1);
+            env.sync();
+        } else {
+            const uint32_t repw = s->rep[r & 1];
+            for (uint32_t p = r0 + tid; p < r1; p += nth) {
+                uint32_t v = 0;
+                if (p + 3 <= n) {
+                    // candidate distances, 0 = none: 1, 2, the head word's two positions, the last match of the round before
+                    uint32_t cd[5] = {p >= 1 ? 1u : 0u, p >= 2 ? 2u : 0u, 0, 0, repw ? (repw & 0xFFFFu) + 1 : 0u};
+                    if (p + 4 <= n) {
+                        const uint32_t h = s->u.head[uq_def_hash(s->in + p)];
+                        s->prev[p - r0] = (uint16_t)(h >> 16);
+                        if (h >> 16) cd[2] = p - ((h >> 16) - 1);
+                        if (h & 0xFFFFu) cd[3] = p - ((h & 0xFFFFu) - 1);
+                    }
+                    const uint32_t lim = n - p < 258 ? n - p : 258;
+                    uint32_t bl = 0, bd = 0;
+                    for (uint32_t k = 0; k < 5; ++k) {
+                        const uint32_t d = cd[k];
+                        if (!d || d > p || d > 32768u) continue;
+                        const uint32_t L = uq_def_common(s->in, p - d, p, lim);
+                        if (L > bl || (L == bl && d < bd)) { bl = L; bd = d; }
+                    }
+                    if (bl >= 3 && !(bl == 3 && bd > 4096)) {
+                        v = uq_def_lcode(bl);
+                        if constexpr (kEmit) env.dist_put(p, bd);
+                        else { uint32_t dv, dn; env.dist_put(p, uq_def_dsym(bd, dv, dn)); }
+                        env.lds_max(&s->rep[(r + 1) & 1], ((p - r0 + 1) << 16) | (bd - 1));
+                    }
+                }
+                s->len[p] = (uint8_t)v;
+            }
+            env.sync();
+            for (uint32_t p = r0 + tid; p < r1; p += nth)
+                if (p + 4 <= n) env.lds_max(&s->u.head[uq_def_hash(s->in + p)], ((p + 1) << 16) | s->prev[p - r0]);
+            if (tid == 0) s->rep[r & 1] = 0;
+            env.sync();
         }
-        env.sync();
-        for (uint32_t p = r0 + tid; p < r1; p += nth)
-            if (p + 4 <= n) env.lds_max(&s->u.head[uq_def_hash(s->in + p)], p + 1);
-        env.sync();
     }
 
-    // ---- 3. greedy parse: the first token start of every sub-segment
+    // ---- 3. parse (greedy; level 2: lazy, see uq_def_tok): the first token start of every sub-segment
     const uint32_t nsub = (n + UQ_DEF_SUB - 1) / UQ_DEF_SUB;
     uint32_t cur = 0;                                                   // thread 0: the chain's next token start
     for (uint32_t w0 = 0; w0 < n; w0 += UQ_DEF_WIN) {
         const uint32_t w1 = w0 + UQ_DEF_WIN < n ? w0 + UQ_DEF_WIN : n;
         for (uint32_t p = w0 + tid; p < w1; p += nth) {
-            const uint32_t v = s->len[p];
+            const uint32_t v = uq_def_tok<kLevel>(s->len, p, n);
             s->u.jmp[p - w0] = (uint16_t)(p + (v ? uq_def_mlen(v) : 1) - w0);
         }
         env.sync();
@@ -304,7 +382,7 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
     for (uint32_t k = tid; k < nsub; k += nth) {
         const uint32_t end = (k + 1) * UQ_DEF_SUB < n ? (k + 1) * UQ_DEF_SUB : n;
         for (uint32_t p = s->entry[k]; p < end;) {
-            const uint32_t v = s->len[p];
+            const uint32_t v = uq_def_tok<kLevel>(s->len, p, n);
             if (!v) { env.lds_add(&s->lfreq[s->in[p]], 1); ++p; continue; }
             uint32_t ev, en;
             const uint32_t L = uq_def_mlen(v);
@@ -372,7 +450,7 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
             const uint32_t end = (k + 1) * UQ_DEF_SUB < n ? (k + 1) * UQ_DEF_SUB : n;
             uint32_t b = 0;
             for (uint32_t p = s->entry[k]; p < end;) {
-                const uint32_t v = s->len[p];
+                const uint32_t v = uq_def_tok<kLevel>(s->len, p, n);
                 if (!v) { b += s->llen[s->in[p]]; ++p; continue; }
                 uint32_t ev, en, dv, dn;
                 const uint32_t L = uq_def_mlen(v);
@@ -410,21 +488,27 @@ UQ_DEF_HD void uq_def_plan(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t 
 
 // The size of the BGZF member that uq_deflate_block writes for s->in[0, n), and nothing written.  Env: sync(), lds_max / lds_add, and
 // dist_put(p, sym) / dist_get(p) (one distance symbol, 0..29, per position: n entries).  The block must already be in s->in.
-template <class Env>
-UQ_DEF_HD int uq_deflate_block_size(Env& env, UqDeflateSizeLds* s, uint32_t n, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+// uq_deflate_block_size_l<2> (Lds = UqDeflateSizeLds2): the size uq_deflate_block_l<2> writes.
+template <int kLevel, class Env, class Lds>
+UQ_DEF_HD int uq_deflate_block_size_l(Env& env, Lds* s, uint32_t n, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
     if (n > UQ_DEF_MAX_IN) return UQ_DEF_TOO_LARGE;
-    uq_def_plan<false>(env, s, n, tid, nth);
+    uq_def_plan<false, kLevel>(env, s, n, tid, nth);
     *member_bytes = s->member_bytes;
     return UQ_DEF_OK;
+}
+template <class Env>
+UQ_DEF_HD int uq_deflate_block_size(Env& env, UqDeflateSizeLds* s, uint32_t n, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+    return uq_deflate_block_size_l<1>(env, s, n, tid, nth, member_bytes);
 }
 
 // Compresses s->in[0, n) into one BGZF member: *member_bytes = its size.  Env: sync(), lds_max / lds_add / lds_xor (atomics on LDS words),
 // dist_put(p, d) / dist_get(p) (the distance workspace, n entries), word_store(w, v) / word_or(w, v) (32-bit word w of the member; the member's
 // words are zero before the call), and x2n (the CRC shift table).  The block must already be in s->in.
-template <class Env>
-UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t cap, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+// uq_deflate_block_l<2> (Lds = UqDeflateLds2): level 2, the same Env.
+template <int kLevel, class Env, class Lds>
+UQ_DEF_HD int uq_deflate_block_l(Env& env, Lds* s, uint32_t n, uint32_t cap, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
     if (n > UQ_DEF_MAX_IN) return UQ_DEF_TOO_LARGE;
-    uq_def_plan<true>(env, s, n, tid, nth);
+    uq_def_plan<true, kLevel>(env, s, n, tid, nth);
     const uint32_t nsub = (n + UQ_DEF_SUB - 1) / UQ_DEF_SUB;
     const uint32_t mb = s->member_bytes;
     *member_bytes = mb;
@@ -497,7 +581,7 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
             const uint32_t k = r - 1, end = (k + 1) * UQ_DEF_SUB < n ? (k + 1) * UQ_DEF_SUB : n;
             UqDefBits<Env> bw(env, s->bits[k]);
             for (uint32_t p = s->entry[k]; p < end;) {
-                const uint32_t v = s->len[p];
+                const uint32_t v = uq_def_tok<kLevel>(s->len, p, n);
                 if (!v) { const uint32_t c = s->in[p]; bw.put(s->lcode[c], s->llen[c]); ++p; continue; }
                 uint32_t ev, en, dv, dn;
                 const uint32_t L = uq_def_mlen(v);
@@ -512,4 +596,9 @@ UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t c
         }
     }
     return UQ_DEF_OK;
+}
+
+template <class Env>
+UQ_DEF_HD int uq_deflate_block(Env& env, UqDeflateLds* s, uint32_t n, uint32_t cap, uint32_t tid, uint32_t nth, uint32_t* member_bytes) {
+    return uq_deflate_block_l<1>(env, s, n, cap, tid, nth, member_bytes);
 }

@@ -396,7 +396,7 @@ class ShardedSession(Session):
             else: text = self.ctx.torch.empty(0, dtype=self.ctx.torch.uint8, device=self.ctx.device)
             if getattr(self.args, 'bgzf', False):
                 # every rank deflates its own text into whole members; the last one appends the EOF member
-                text = self.ops.bgzf_compress(self.ctx, text, eof=self.rank == self.world - 1)
+                text = self.ops.bgzf_compress(self.ctx, text, eof=self.rank == self.world - 1, level=self.bgzf_level)
             return text, lo, n
         text, lo, n = self.guarded(my_text, 'decoding ' + str(self.args.input))
         if os.environ.get('UQ_TIMING') and self.inflated_members is not None:

@@ -774,6 +774,14 @@ def gzip_stream_host(data, chunk_bytes, starts=None):
 BGZF_BLOCK = 65280
 BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')
 DEFLATE_STATUS = {1: 'the member needs more than the output capacity', 2: 'more than 65 280 input bytes'}
+BGZF_LEVELS = (1, 2)
+UQ_BGZF_EOF, UQ_BGZF_LEVEL2 = 1, 2
+
+
+def bgzf_level_flags(level):
+    """The flag bits of a compressor level: 1 (the default: one candidate per position, greedy) or 2 (more candidates, lazy)."""
+    if level not in BGZF_LEVELS: raise ValueError('the BGZF compressor has levels 1 and 2, not %r' % (level,))
+    return UQ_BGZF_LEVEL2 if level == 2 else 0
 
 
 def bgzf_bound(nbytes):
@@ -783,14 +791,15 @@ def bgzf_bound(nbytes):
     return out.value
 
 
-def bgzf_compress(ctx, d_text, eof=True):
+def bgzf_compress(ctx, d_text, eof=True, level=1):
     """uq_bgzf_compress: the uint8 device tensor d_text as a BGZF stream (one member per 65 280 bytes, deflated on the device, plus the EOF
-    member when `eof`).  Returns a uint8 device tensor of exactly the stream's bytes."""
+    member when `eof`) at compressor level `level`.  Returns a uint8 device tensor of exactly the stream's bytes."""
+    flags = bgzf_level_flags(level) | (UQ_BGZF_EOF if eof else 0)
     t = ctx.torch
     n = d_text.numel()
     out = t.empty(bgzf_bound(n), dtype=t.uint8, device=ctx.device)
     nout = C.c_uint64()
-    call('uq_bgzf_compress', ctx.h, _p(d_text) if n else C.c_void_p(0), n, _p(out), out.numel(), C.byref(nout), 1 if eof else 0)
+    call('uq_bgzf_compress', ctx.h, _p(d_text) if n else C.c_void_p(0), n, _p(out), out.numel(), C.byref(nout), flags)
     return out[:nout.value]
 
 
@@ -818,42 +827,46 @@ def bgzf_parts_bound(parts):
     return out.value
 
 
-def bgzf_compress_parts(ctx, parts, eof=False, capacity=None):
+def bgzf_compress_parts(ctx, parts, eof=False, capacity=None, level=1):
     """uq_bgzf_compress_parts: parts = [(prefix bytes (<= 256), device tensor)]; every part's prefix + data as BGZF members, the block cuts
     restarting at each part, all parts compressed in one run.  Returns (uint8 device tensor of the members of all parts in order, [bytes
-    of each part]).  `capacity`: the output buffer's size instead of bgzf_parts_bound's."""
+    of each part]).  `capacity`: the output buffer's size instead of bgzf_parts_bound's; `level`: the compressor level."""
+    flags = bgzf_level_flags(level) | (UQ_BGZF_EOF if eof else 0)
     t = ctx.torch
     arr, keep = _bgzf_parts_arg(parts)
     cap = bgzf_parts_bound(parts) if capacity is None else int(capacity)
     out = t.empty(cap, dtype=t.uint8, device=ctx.device)
     sizes = (C.c_uint64 * max(len(parts), 1))()
     nout = C.c_uint64()
-    call('uq_bgzf_compress_parts', ctx.h, arr, len(parts), _p(out) if cap else C.c_void_p(0), cap, sizes, C.byref(nout), 1 if eof else 0)
+    call('uq_bgzf_compress_parts', ctx.h, arr, len(parts), _p(out) if cap else C.c_void_p(0), cap, sizes, C.byref(nout), flags)
     return out[:nout.value], [int(sizes[k]) for k in range(len(parts))]
 
 
-def bgzf_compress_parts_host(parts, eof=False):
+def bgzf_compress_parts_host(parts, eof=False, level=1):
     """The host twin of bgzf_compress_parts over host bytes: parts = [(prefix bytes, data bytes)].  Returns (bytes, [bytes of each part])."""
     out, sizes = [], []
     for prefix, data in parts:
         whole = bytes(prefix) + bytes(data)
-        members = [bgzf_block_host(whole[o:o + BGZF_BLOCK]) for o in range(0, len(whole), BGZF_BLOCK)]
+        members = [bgzf_block_host(whole[o:o + BGZF_BLOCK], level=level) for o in range(0, len(whole), BGZF_BLOCK)]
         sizes.append(sum(len(m) for m in members))
         out.extend(members)
     if eof: out.append(BGZF_EOF)
     return b''.join(out), sizes
 
 
-def bgzf_block_host(data, capacity=None):
+def bgzf_block_host(data, capacity=None, level=1):
     """uq_bgzf_compress_block_host: one block (<= 65 280 bytes) through the device compressor's code on the CPU.  Returns the member's
-    bytes; with `capacity`, returns (status, member size, the capacity's bytes) instead."""
+    bytes; with `capacity`, returns (status, member size, the capacity's bytes) instead.  `level` 2: uq_bgzf_compress_block_host_l with
+    UQ_BGZF_LEVEL2."""
+    flags = bgzf_level_flags(level)
     data = bytes(data)
     src = np.frombuffer(data, dtype=np.uint8)
     cap = 65536 if capacity is None else int(capacity)
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     nout, st = C.c_uint64(), C.c_uint32()
-    call('uq_bgzf_compress_block_host', C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), cap,
-         C.byref(nout), C.byref(st))
+    args = (C.c_void_p(src.ctypes.data if src.size else 0), len(data), C.c_void_p(out.ctypes.data), cap, C.byref(nout), C.byref(st))
+    if flags: call('uq_bgzf_compress_block_host_l', *args, flags)
+    else: call('uq_bgzf_compress_block_host', *args)
     if capacity is not None:
         return st.value, nout.value, out[:cap].tobytes()
     if st.value:
@@ -862,14 +875,17 @@ def bgzf_block_host(data, capacity=None):
 
 
 # ------------------------------------------------------------------ the size of a buffer as BGZF (the --test sizer)
-def deflate_size_host(data, prefix=b''):
-    """uq_deflate_size_host: S(prefix + data) on the CPU -- the bytes ops.bgzf_compress(prefix + data, eof=False) would have."""
+def deflate_size_host(data, prefix=b'', level=1):
+    """uq_deflate_size_host: S(prefix + data) on the CPU -- the bytes ops.bgzf_compress(prefix + data, eof=False) would have at that level."""
+    flags = bgzf_level_flags(level)
     data, prefix = bytes(data), bytes(prefix)
     src = np.frombuffer(data, dtype=np.uint8)
     pre = np.frombuffer(prefix, dtype=np.uint8)
     out = C.c_uint64()
-    call('uq_deflate_size_host', C.c_void_p(pre.ctypes.data if pre.size else 0), len(prefix), C.c_void_p(src.ctypes.data if src.size else 0),
-         len(data), C.byref(out))
+    args = (C.c_void_p(pre.ctypes.data if pre.size else 0), len(prefix), C.c_void_p(src.ctypes.data if src.size else 0), len(data),
+            C.byref(out))
+    if flags: call('uq_deflate_size_host_l', *args, flags)
+    else: call('uq_deflate_size_host', *args)
     return out.value
 
 
@@ -877,8 +893,9 @@ class DeflateSizes:
     """uq_deflate_size for up to `capacity` buffers: add() queues one (nothing is read back, the stream is not synchronised), fetch()
     reads all the totals back at once.  A buffer passed to add() may be overwritten by work queued behind it on the context's stream."""
 
-    def __init__(self, ctx, capacity):
+    def __init__(self, ctx, capacity, level=1):
         self.ctx, self.capacity, self.n = ctx, int(capacity), 0
+        self.flags = bgzf_level_flags(level)
         self.slots = ctx.torch.zeros(2 * self.capacity, dtype=ctx.torch.int64, device=ctx.device)      # totals, then one status each
 
     def add(self, prefix, d_data):
@@ -886,8 +903,10 @@ class DeflateSizes:
         if self.n >= self.capacity: raise ValueError('DeflateSizes: more than %d buffers' % self.capacity)
         prefix = bytes(prefix)
         nbytes = d_data.numel() * d_data.element_size()
-        call('uq_deflate_size', self.ctx.h, prefix, len(prefix), _p(d_data) if nbytes else C.c_void_p(0), nbytes,
-             _p(self.slots[self.n:]), _p(self.slots[self.capacity + self.n:]))
+        args = (self.ctx.h, prefix, len(prefix), _p(d_data) if nbytes else C.c_void_p(0), nbytes, _p(self.slots[self.n:]),
+                _p(self.slots[self.capacity + self.n:]))
+        if self.flags: call('uq_deflate_size_l', *args, self.flags)
+        else: call('uq_deflate_size', *args)
         self.n += 1
         return self.n - 1
 
@@ -898,8 +917,8 @@ class DeflateSizes:
         return [int(v) for v in host[:self.n]]
 
 
-def deflate_size(ctx, prefix, d_data):
+def deflate_size(ctx, prefix, d_data, level=1):
     """S(prefix + the bytes of d_data) for one buffer (queue, then read back)."""
-    q = DeflateSizes(ctx, 1)
+    q = DeflateSizes(ctx, 1, level=level)
     q.add(prefix, d_data)
     return q.fetch()[0]

@@ -77,6 +77,9 @@ def build_parser():
     p.add_argument('--device-compressor', action='store_true', default=False,
                    help='with --test: size every candidate on the GPU with the built-in deflate sizer (its size as BGZF from this '
                         "project's own compressor) instead of piping it through --compressor (extension)")
+    p.add_argument('--bgzf-level', type=int, default=None, metavar='{1,2}',
+                   help='the level of the GPU deflate compressor under --decode --bgzf, --gz and --test --device-compressor: 1 (the default, '
+                        'fast) or 2 (more match candidates and a lazy parse: smaller, slower) (extension)')
     return p
 
 
@@ -100,6 +103,12 @@ def validate_args(args):
     if getattr(args, 'device_compressor', False):
         if args.compressor: error('ERROR: --device-compressor and --compressor are two ways to size the same candidates: give one of them')
         if not args.test: error('ERROR: --device-compressor sizes the candidates of --test: use it together with --test')
+    if getattr(args, 'bgzf_level', None) is not None:
+        if args.bgzf_level not in (1, 2): error('ERROR: --bgzf-level is 1 or 2')
+        if not ((getattr(args, 'bgzf', False) and args.decode) or getattr(args, 'gz', False) or
+                (getattr(args, 'device_compressor', False) and args.test)):
+            error('ERROR: --bgzf-level sets the level of the GPU deflate compressor: use it together with --decode --bgzf, --gz or '
+                  '--test --device-compressor')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     return args
 
@@ -498,6 +507,11 @@ class Session:
         return bool(getattr(self.args, 'device_compressor', False))
 
     @property
+    def bgzf_level(self):
+        """--bgzf-level: the level of every run of the device compressor and of its host twin (1 when not given)."""
+        return getattr(self.args, 'bgzf_level', None) or 1
+
+    @property
     def has_compressor(self):
         """--compressor CMD or --device-compressor: the candidates of --test are sized by something."""
         return self.args.compressor is not None or self.device_sizer
@@ -507,7 +521,7 @@ class Session:
         tensor): the member is the .npy header `data` followed by the bytes of a device tensor, which stay where they are -- with
         --device-compressor its size as BGZF (uq_deflate_size), otherwise the member goes to the host and through the command."""
         if tensor is not None:
-            if self.device_sizer: return self.ops.deflate_size(self.ctx, data, tensor)
+            if self.device_sizer: return self.ops.deflate_size(self.ctx, data, tensor, level=self.bgzf_level)
             data = data + self.ctx.to_numpy(tensor).tobytes()
         if not self.args.compressor: return len(data)
         p = subprocess.run(self.args.compressor + ' | wc -c', shell=True, input=data, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
@@ -527,7 +541,7 @@ class Session:
         pats = PATTERNS if pattern is None else [pattern]
         if self.device_sizer:
             # every layout into the one table-sized buffer and sized there, queued back to back; the totals come back together
-            sizes = self.ops.DeflateSizes(self.ctx, len(pats))
+            sizes = self.ops.DeflateSizes(self.ctx, len(pats), level=self.bgzf_level)
             payload = self.ctx.empty(rows * cols)
             for pat in pats:
                 self.ops.pattern(self.ctx, t, rows, cols, pat, out=payload)
@@ -745,8 +759,8 @@ class Session:
                 header, payload = b'', ctx.bytes_to_device(header)
             parts.append((header, payload))
             sizes.append(len(header) + (0 if payload is None else payload.numel() * payload.element_size()))
-        frames = [ops.bgzf_block_host(f) for f in container.framing_pieces([(e[0], n) for e, n in zip(entries, sizes)], mtime)]
-        d_out, part_bytes = ops.bgzf_compress_parts(ctx, parts)
+        frames = [ops.bgzf_block_host(f, level=self.bgzf_level) for f in container.framing_pieces([(e[0], n) for e, n in zip(entries, sizes)], mtime)]
+        d_out, part_bytes = ops.bgzf_compress_parts(ctx, parts, level=self.bgzf_level)
         layout = container.member_aligned_layout([len(f) for f in frames], part_bytes)
         src = 0
         for k, entry in enumerate(layout):
@@ -932,7 +946,7 @@ class Session:
         if self.device_text_possible(config):
             # the text streams out through the pinned buffers (--bgzf: deflated on the device first)
             text = self.decode_text(config, DNA, QUAL, d_cols)
-            self.io.device_to_stream(self.ops.bgzf_compress(ctx, text) if bgzf else text, w)
+            self.io.device_to_stream(self.ops.bgzf_compress(ctx, text, level=self.bgzf_level) if bgzf else text, w)
         else:
             seq, qt, ln = self.split_bits(DNA, QUAL, config)
             dmax = config['dna_max']
@@ -945,7 +959,7 @@ class Session:
                 sink.write(names[r].encode('latin-1') + b'\n' + S[r, :l].tobytes() + b'\n+\n' + Q[r, :l].tobytes() + b'\n')
             if bgzf:
                 # the host-built text goes up to the device and is deflated there like the device text
-                self.io.device_to_stream(self.ops.bgzf_compress(ctx, ctx.bytes_to_device(sink.getvalue())), w)
+                self.io.device_to_stream(self.ops.bgzf_compress(ctx, ctx.bytes_to_device(sink.getvalue()), level=self.bgzf_level), w)
 
 
 # ---------------------------------------------------------------------- the packers with the reference's own signature
