@@ -337,6 +337,41 @@ def cases():
     yield 'alpha_mixed_case', custom(300, 37, 'ACGTacgt', [chr(40 + k) for k in range(12)], 6), RAW, False
     yield 'var_tiny_alphabets', custom(300, (5, 23), 'ACG', '#5I', 7), RAW, False
 
+    # ---- the geometries bench.py and the headline numbers run on.  Everything above stops at 100 bp fixed, 75 bp variable and 22 000 reads.
+    # 28. 150 bp fixed: 38-byte DNA rows, 113-byte QUAL rows, a row ends in a partial group (150 = 18 x 8 + 6); ~ 48 records to a 16 KiB pack
+    #     tile, so 1000 reads are ~ 20 tiles with a record across every tile edge.  Raw, and sorted on DNA with both tables keyed
+    yield 'bench_150bp_raw', synth.fastq(S + 30, 1000, 150), ['--sort', 'None', '--raw', 'DNA', 'QUAL', 'QNAME', '--pattern', '0.1', '0.1'], False
+    yield 'bench_150bp_sort_dna_keyed_stable', synth.fastq(S + 31, 600, 150, dup='both', dup_templates=40), ['--sort', 'DNA', '--pattern', '1.2', '3.1'], True
+    # 29. 36-301 bp variable (L % 4 != 0 only: Q7): 76- / 227-byte rows with the N-trick, 114-byte DNA rows with --notricks
+    var301 = synth.fastq(S + 32, 800, (36, 301), n_rate=1, skip_len_mod4=True)
+    yield 'bench_var_36_301', var301, RAW, False
+    yield 'bench_var_36_301_notricks', var301, ['--notricks'] + RAW, False
+    # 30. the THIRD checkpoint of uq.py:586-602 (entries_read == 40 000) and the final check at 45 000 reads.  Columns 1-4 hold 7 + 17 k: the
+    #     largest value minus the smallest exceeds 65 535, so a column that is still a mapping is written as a mapping of strings and the
+    #     config tells which check fired.  Distinct values among reads [0, T] for T = 10 000 / 20 000 / 40 000 / 44 999:
+    #       column 1: 1000 / 2000 / 4200 / 4200 -> integers by the 40 000 checkpoint alone (4200 > 4000)
+    #       column 2: 1000 / 2000 / 4000 / 4000 -> stays a mapping (4000 is not > 4000)
+    #       column 3: 1000 / 2000 / 4000 / 4500 -> integers by the final check alone (4500 > 44 999 // 10)
+    #       column 4: 1000 / 2000 / 4000 / 4499 -> stays a mapping (4499 is not > 4499)
+    #     A value appears for the first time in the reads right behind a checkpoint; every other read repeats one of the first six values, and the
+    #     reads are 1 bp, which keeps the file under 1 MiB.  Column 5 is small
+    def demote40k(i):
+        def col(c, steps):
+            seen, since = 6, 5                          # k = 0 .. 5 are the first six reads
+            for upto, distinct in steps:
+                if since < i <= upto and i - since <= distinct - seen: return seen + i - since - 1
+                if i <= upto: break
+                seen, since = distinct, upto
+            return (i * (2 * c + 1) + c) % 6
+        k = [col(c, steps) for c, steps in enumerate([
+            [(10000, 1000), (20000, 2000), (40000, 4200)],
+            [(10000, 1000), (20000, 2000), (40000, 4000)],
+            [(10000, 1000), (20000, 2000), (40000, 4000), (44999, 4500)],
+            [(10000, 1000), (20000, 2000), (40000, 4000), (44999, 4499)]])]
+        if i < 6: k = [i] * 4
+        return b'@%d:%d:%d:%d:%d' % (7 + 17 * k[0], 7 + 17 * k[1], 7 + 17 * k[2], 7 + 17 * k[3], i % 3)
+    yield 'qn_demote_40000', rename(synth.fastq(S + 33, 45000, 1), demote40k), RAW, False
+
 
 if __name__ == '__main__':
     only = set(a for a in sys.argv[1:] if not a.startswith('--'))

@@ -279,7 +279,8 @@ def test_pack_reports_uncoded_symbol(ctx):
 
 
 @pytest.mark.parametrize('name', ['cfg1_10k_100bp', 'fixed_n_newcode', 'variable_ntrick', 'variable_notricks', 'fixed_pad', 'alpha_iupac_4bit', 'qual_7bit', 'qual_8bit',
-                                  'two_ntrick_bases', 'one_base_one_qual', 'alpha_mixed_case', 'var_tiny_alphabets'])
+                                  'two_ntrick_bases', 'one_base_one_qual', 'alpha_mixed_case', 'var_tiny_alphabets',
+                                  'bench_150bp_raw', 'bench_var_36_301', 'bench_var_36_301_notricks', 'qn_demote_40000'])
 def test_pack_matches_reference_golden(ctx, name):
     """DNA.raw / QUAL.raw written by the reference itself (tests/golden/*.uQ) == the HIP packers' rows."""
     meta = json.load(open(os.path.join(GOLD, name + '.json')))
@@ -424,6 +425,62 @@ def test_default_encode_form_against_the_oracle(ctx, name, n, length, kw, dk, qn
             oarr = O.qname_encode(lines, p1['prefix'], p1['suffix'], p1['separators'], ocols)
             assert got is not None and list(got[:3]) == [p1['prefix'], p1['suffix'], p1['separators']] and got[3] == ocols
             for a, b in zip(got[4], oarr): assert np.array_equal(ctx.to_numpy(a, b.dtype), b)
+
+
+GOLDEN_DEFAULT_FORM = ['bench_150bp_raw', 'bench_var_36_301', 'bench_var_36_301_notricks', 'cfg1_10k_100bp', 'variable_ntrick', 'variable_notricks']
+
+
+@pytest.mark.parametrize('qn', [False, True], ids=['plain', 'qname-phase'])
+@pytest.mark.parametrize('name', GOLDEN_DEFAULT_FORM)
+def test_default_encode_form_matches_reference_golden(ctx, name, qn):
+    """The launch sequence of test_default_encode_form_against_the_oracle -- census lists, pack + statistics (+ QNAME fields) in one launch --
+    against bytes the REFERENCE wrote (tests/golden/*.uQ), the benchmark's geometries among them (150 bp: 38- / 113-byte rows that end in a
+    partial group; 36-301 bp: 76- / 227-byte rows, 114-byte rows at three bits): the decisions that follow from the kernel's statistics are
+    config.json's, the rows are DNA.raw / QUAL.raw, and the QNAME layout, column types and column arrays are the config's and QNAME_k.raw."""
+    meta = json.load(open(os.path.join(GOLD, name + '.json')))
+    cfg, members = O.read_tar(os.path.join(GOLD, name + '.uQ'))
+    assert cfg['sort'] == [None] and cfg['pattern'] == ['0.1', '0.1']
+    dk = dict(notricks='--notricks' in meta['flags'], pad='--pad' in meta['flags'])
+    host = np.frombuffer(open(os.path.join(GOLD, name + '.fastq'), 'rb').read(), dtype=np.uint8).copy()
+    n = cfg['reads']
+    decided = ('bases', 'qualities', 'N_qual', 'bits_per_base', 'bits_per_quality', 'variable_read_lengths', 'dna_max')
+    ref = oracle_c.stats(host, oracle_c.index_lines(host), 0, n)
+    d = _decide_from_stats(type('H', (), dict(counts=ref['counts'], len_min=ref['len_min'], len_max=ref['len_max'], nz_keys=None))(), **dk)
+    assert all(d[k] == cfg[k] for k in decided)
+    ref_dna, ref_qual = O.unpattern(members['DNA.raw']), O.unpattern(members['QUAL.raw'])
+    assert ref_dna.shape == (n, d['dna_bytes_per_row']) and ref_qual.shape == (n, d['quality_bytes_per_row'])
+    p = ops.make_pack_params(d['bases'], d['qualities'], d['N_qual'], d['bits_per_base'], d['bits_per_quality'], d['variable_read_lengths'],
+                             d['dna_bytes_per_row'], d['quality_bytes_per_row'], d['dna_max'], ref['max_record_bytes'], avg_record_bytes=host.size // n)
+    for rep in range(2):                                                          # twice: the second launch starts from the first one's LDS
+        ops.scribble_lds(ctx, 0x5EED0000 + rep) if rep == 0 else None
+        d_buf = ctx.to_device(host)
+        cen = ops.ChunkedCensus(ctx, d_buf); cen.chunk(0, d_buf.numel()); cen.end_async()
+        fq = None
+        if qn:
+            fq = ops.FusedQname(ctx, n + 7)
+            ops.qname_guess_async(ctx, d_buf, None, fq)
+        q = ops.pack_stats_async(ctx, d_buf, None, n + 7, p, fq=fq)
+        assert q is not None
+        if qn: ops.qname_fused_finish(ctx, fq)
+        hs = ops.stats_fetch(ctx, q[3])
+        nl, ok = cen.wait()
+        assert ok and nl == 4 * n and not hs.incomplete
+        got = _decide_from_stats(hs, **dk)
+        for k in decided: assert got[k] == cfg[k], k
+        assert (got['dna_bytes_per_row'], got['quality_bytes_per_row']) == (ref_dna.shape[1], ref_qual.shape[1])
+        assert np.array_equal(ctx.to_numpy(q[0][:n * ref_dna.shape[1]]).reshape(n, -1), ref_dna), 'DNA rows differ from the reference\'s DNA.raw'
+        assert np.array_equal(ctx.to_numpy(q[1][:n * ref_qual.shape[1]]).reshape(n, -1), ref_qual), 'QUAL rows differ from the reference\'s QUAL.raw'
+        assert ops.bad_index(q[2]) is None
+        if qn:
+            from uq_amd import qname_device
+            ans = qname_device.analyse_fused(ctx, fq, n)
+            assert ans is not None, 'the fused QNAME pass declined the synthetic Illumina names it is built for'
+            assert list(ans[:3]) == [cfg['QNAME_prefix'], cfg['QNAME_suffix'], cfg['QNAME_separators']]
+            assert json.loads(json.dumps(ans[3])) == cfg['QNAME_columns']
+            assert len(ans[4]) == len(cfg['QNAME_columns'])
+            for a, c in zip(ans[4], cfg['QNAME_columns']):
+                want = O.unpattern(members[c['name'] + '.raw'])
+                assert want.dtype == np.dtype(c['dtype']) and np.array_equal(ctx.to_numpy(a, want.dtype), want), c['name']
 
 
 def test_pack_stats_wrong_guesses(ctx):

@@ -203,23 +203,103 @@ def msd(ctx):
     ops.sort_config(ctx)
 
 
+def _heads_spread(T):
+    """Which way round 0 of a row sort goes once the MSD partition is switched on for every row count (sort.hip round 0, msd.hip's header),
+    restated from the rows alone.  A row's head is its first eight bytes as a big-endian number, z the leading bits all heads share.  The
+    partition takes a table of two rows and more whose heads differ within their first 40 bits (z < 40) and whose heaviest bucket of the
+    plan's T = max(8, ceil(log2(n / 64))) leading bits behind z holds at most a finishing chunk of 1024 rows; everything else is handed back
+    to the LSD passes.  (The product guesses both from 4096 sampled rows: a shape within a factor two of the 1024 is not a case for this.)"""
+    n, C = T.shape
+    if n < 2: return False
+    H = np.zeros((n, 8), dtype=np.uint8); H[:, :min(C, 8)] = T[:, :8]
+    h = H.view('>u8').ravel().astype(np.uint64)
+    same = ~(int(np.bitwise_and.reduce(h)) ^ int(np.bitwise_or.reduce(h))) & (2 ** 64 - 1)
+    z = 0
+    while z < 64 and (same >> (63 - z)) & 1: z += 1
+    if z >= 40: return False
+    bits = max(8, int((n + 63) // 64 - 1).bit_length())
+    heaviest = int(np.bincount(((h << np.uint64(z)) >> np.uint64(64 - bits)).astype(np.int64)).max())
+    assert not 512 <= heaviest <= 2048, 'a borderline shape: the sample may estimate it either way'
+    return heaviest <= 1024
+
+
+# SORT_CASES by _heads_spread, spelled out.  Handed back: a single row; rows that share their first 8 bytes and more (prefix >= 8: z = 64); three
+# row values over 10 000 rows (3 400 rows on one head).  Taken: everything else -- 300 or 7 values over a few thousand rows included, whose
+# heaviest bucket (about 100 and 150 rows) fits a finishing chunk: few distinct heads alone send no table back, a head heavier than a chunk does.
+MSD_TAKES = {(1, 5, 1, 0): False, (2, 1, 2, 0): True, (1000, 1, 7, 0): True, (5000, 8, 5000, 0): True, (5000, 38, 300, 0): True,
+             (20000, 38, 20000, 0): True, (9000, 113, 500, 40): False, (3000, 227, 50, 100): False, (4096, 16, 16, 8): False,
+             (10000, 9, 3, 0): False, (70000, 14, 60000, 0): True}
+
+
 @pytest.mark.parametrize('n,C,nd,prefix', SORT_CASES, ids=lambda v: str(v))
 def test_msd_round0_small_shapes(ctx, msd, n, C, nd, prefix):
     """The shapes of test_argsort_rows_stable / test_unique_rows through the MSD partition: order, stability, unique, inverse == numpy.
-    Tables of few distinct heads are handed back to the LSD passes (the counters say which way a sort went); the answer is the same."""
+    Tables whose heads do not spread (_heads_spread) are handed back to the LSD passes and the others are not: the counters say which way a
+    sort went, and it must be the way MSD_TAKES lists; the answer is the same."""
     rng = np.random.RandomState(n + 7 * C)
     T = _rows_with_dups(rng, n, C, nd, prefix)
     d_T = _dev(ctx, T.ravel())
+    before = ops.sort_counters(ctx)
     perm = ctx.to_numpy(ops.argsort_rows(ctx, d_T, n, C), np.uint32).astype(np.int64)
+    after = ops.sort_counters(ctx)
     assert np.array_equal(perm, O.argsort_rows(T))
-    went = msd()
-    spread = nd >= 5000 and prefix == 0
-    assert went == (1 if spread else went), 'a table of %d distinct random rows did not take the MSD partition' % nd
+    spread = _heads_spread(T)
+    assert spread == MSD_TAKES[(n, C, nd, prefix)]
+    if spread:
+        assert (after[0], after[1]) == (before[0] + 1, before[1]), 'a table whose heads spread did not take the MSD partition'
+    else:
+        assert after[1] > before[1] and after[0] == before[0], 'a table whose heads do not spread was not handed back to the LSD passes'
     perm2, key, skey, uniq, nu = ops.unique_rows(ctx, d_T, n, C)
     ru, rkey = O.unique_rows(T)
     assert nu == len(ru) and np.array_equal(ctx.to_numpy(uniq).reshape(nu, C), ru)
     assert np.array_equal(ctx.to_numpy(key, np.uint32).astype(np.int64), rkey)
     assert np.array_equal(ctx.to_numpy(perm2, np.uint32).astype(np.int64), np.argsort(rkey, kind='stable'))
+
+
+@pytest.fixture(scope='module')
+def bench150_sorted(ctx):
+    """bench_150bp_sort_dna_keyed_stable packed by the HIP packer (38- and 113-byte rows) + the members the reference wrote for it."""
+    import json
+    import os
+    from test_gpu_pack import GOLD, _decide_from_stats, _gpu_pack, _index
+    name = 'bench_150bp_sort_dna_keyed_stable'
+    cfg, members = O.read_tar(os.path.join(GOLD, name + '.uQ'))
+    assert json.load(open(os.path.join(GOLD, name + '.json')))['stable_patch'] and cfg['sort'] == 'DNA' and cfg['pattern'] == ['1.2', '3.1']
+    host = np.frombuffer(open(os.path.join(GOLD, name + '.fastq'), 'rb').read(), dtype=np.uint8).copy()
+    d_buf = ctx.to_device(host)
+    nlines, ls = _index(ctx, d_buf)
+    n = nlines // 4
+    st = ops.stats_new(ctx)
+    ops.stats_accumulate(ctx, st, d_buf, ls, 0, n)
+    hs = ops.stats_fetch(ctx, st)
+    d = _decide_from_stats(hs, first_seen=ops.first_occurrence(ctx, d_buf, ls, 0, n))
+    assert all(d[k] == cfg[k] for k in ('bases', 'qualities', 'N_qual', 'bits_per_base', 'bits_per_quality', 'dna_max', 'variable_read_lengths'))
+    dna, qual, bad = _gpu_pack(ctx, d_buf, ls, n, d, hs.max_record_bytes)
+    assert bad is None and n == cfg['reads'] == 600 and dna.shape == (n, 38) and qual.shape == (n, 113)
+    return dna, qual, cfg, members
+
+
+@pytest.mark.parametrize('form', ['lsd', 'msd'])
+def test_unique_rows_match_reference_tables(ctx, bench150_sorted, form, request):
+    """uq_unique_rows on the benchmark's row widths against bytes the REFERENCE wrote (uq.py:782-802 under the Q17 stable patch): the unique
+    tables are its DNA and QUAL members, the DNA key in sorted order its DNA.key, the QUAL key taken through the DNA permutation its QUAL.key;
+    LSD passes and MSD partition alike."""
+    if form == 'msd': request.getfixturevalue('msd')
+    else: ops.sort_config(ctx, msd_min_rows=-1); request.addfinalizer(lambda: ops.sort_config(ctx))
+    dna, qual, cfg, members = bench150_sorted
+    n = len(dna)
+    load = lambda k: O.unpattern(members[k])
+    ref_dna, ref_qual = O.unpattern(members['DNA'], cfg['pattern'][0]), O.unpattern(members['QUAL'], cfg['pattern'][1])
+    perm, key, skey, uniq, nu = ops.unique_rows(ctx, _dev(ctx, dna.ravel()), n, 38)
+    assert 1 < nu < n and nu == len(ref_dna) and np.array_equal(ctx.to_numpy(uniq).reshape(nu, 38), ref_dna)
+    assert ops.key_itemsize(nu - 1) == load('DNA.key').dtype.itemsize
+    assert np.array_equal(ctx.to_numpy(skey, np.uint32).astype(np.int64), load('DNA.key').astype(np.int64))
+    order = ctx.to_numpy(perm, np.uint32).astype(np.int64)
+    assert np.array_equal(ctx.to_numpy(key, np.uint32).astype(np.int64)[order], load('DNA.key').astype(np.int64))
+    qperm, qkey, qskey, quniq, qnu = ops.unique_rows(ctx, _dev(ctx, qual.ravel()), n, 113)
+    assert 1 < qnu < n and qnu == len(ref_qual) and np.array_equal(ctx.to_numpy(quniq).reshape(qnu, 113), ref_qual)
+    assert ops.key_itemsize(qnu - 1) == load('QUAL.key').dtype.itemsize
+    assert np.array_equal(ctx.to_numpy(qkey, np.uint32).astype(np.int64)[order], load('QUAL.key').astype(np.int64))
 
 
 MSD_CASES = [

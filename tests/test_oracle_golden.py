@@ -5,6 +5,7 @@ import glob
 import io
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +13,9 @@ import pytest
 import uq_oracle as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+sys.path.insert(0, GOLD)
+import inflate_inputs                                           # the larger text fixtures are committed as .fastq.gz: the plain files, if the build has not written them
+INFLATED = inflate_inputs.inflate(GOLD)
 GOLDEN = sorted(os.path.basename(f)[:-5] for f in glob.glob(os.path.join(GOLD, '*.json')))
 REFUSED = [n for n in GOLDEN if n.endswith('_refused')]        # inputs the reference itself gives up on: the fixture is the refusal
 WRITTEN = [n for n in GOLDEN if n not in REFUSED]
@@ -33,10 +37,18 @@ def flags_to_kwargs(flags):
 
 
 def test_golden_set_is_complete():
-    assert len(WRITTEN) >= 40 and len(REFUSED) >= 6
+    assert len(WRITTEN) >= 45 and len(REFUSED) >= 6
     for name in GOLDEN:
         for ext in ('.fastq', '.json') + (() if name in REFUSED else ('.uQ',)):
             assert os.path.exists(os.path.join(GOLD, name + ext))
+    # a fixture's text is committed plain or compressed, never both ways (git ignores the plain file of a compressed one), none above 1 MiB
+    import shutil
+    import subprocess
+    tracked = subprocess.run(['git', 'ls-files', '--', GOLD], capture_output=True, text=True, cwd=GOLD) if shutil.which('git') else None
+    if tracked is not None and tracked.returncode == 0 and tracked.stdout:
+        files = set(os.path.basename(f) for f in tracked.stdout.split())
+        assert not [f for f in files if f.endswith('.gz') and f[:-3] in files]
+    assert len(INFLATED) >= 9 and all(os.path.getsize(p + '.gz') < 1 << 20 and os.path.getsize(p) < 1 << 20 for p in INFLATED)
     for name in REFUSED:
         meta = json.load(open(os.path.join(GOLD, name + '.json')))
         assert meta['reference_refuses'] and meta['reference_says'] and not os.path.exists(os.path.join(GOLD, name + '.uQ'))
@@ -63,6 +75,54 @@ def test_golden_set_covers_the_width_ladder():
         cfg, _ = O.read_tar(os.path.join(GOLD, name + '.uQ'))
         bd.add(cfg['bits_per_base']); bq.add(cfg['bits_per_quality']); ntrick.add(len(cfg['N_qual']))
     assert bd >= {2, 3, 4} and bq >= {2, 4, 5, 6, 7, 8} and ntrick >= {0, 1, 2}, (bd, bq, ntrick)
+
+
+def test_golden_set_covers_the_benchmark_geometries():
+    """The shapes bench.py and the headline numbers run on occur in a reference-written container: 150 bp fixed (38- / 113-byte rows, a row ends
+    in a partial group: 150 = 18 x 8 + 6), 36-301 bp variable at 2-bit (76 / 227) and at 3-bit bases (114), and a file beyond the 40 000-read
+    checkpoint of the QNAME column typing (uq.py:586-602, 634-636)."""
+    fixed150 = var301 = var301_3bit = beyond_40000 = False
+    for name in WRITTEN:
+        cfg, members = O.read_tar(os.path.join(GOLD, name + '.uQ'))
+        beyond_40000 |= cfg['reads'] > 40001
+        if 'DNA.raw' not in members or 'QUAL.raw' not in members: continue
+        dna, qual = O.unpattern(members['DNA.raw'], cfg['pattern'][0]), O.unpattern(members['QUAL.raw'], cfg['pattern'][1])
+        assert dna.shape[0] == qual.shape[0] == cfg['reads']
+        rows = (cfg['bits_per_base'], dna.shape[1], qual.shape[1])
+        if not cfg['variable_read_lengths'] and cfg['dna_max'] == 150: fixed150 |= rows == (2, 38, 113)
+        if cfg['variable_read_lengths'] and cfg['dna_max'] == 301:
+            var301 |= rows == (2, 76, 227)
+            var301_3bit |= rows[:2] == (3, 114)
+    assert fixed150 and var301 and var301_3bit and beyond_40000, (fixed150, var301, var301_3bit, beyond_40000)
+
+
+def test_checkpoint_fixture_is_what_it_claims():
+    """qn_demote_40000 from its own bytes, through no project code: the distinct strings of each column over reads [0, T] at the three
+    checkpoints (entries_read == 10 000 / 20 000 / 40 000, uq.py:634-636) and at the final check (entries_read == 44 999, uq.py:638) stand
+    where `len(map) > entries_read / 10` (uq.py:590) tells `>` from `>=`; and the reference's config.json says which check fired: a column
+    that is still a mapping is one of strings (its values span more than 65 535, uq.py:652), a demoted one is integers."""
+    import tarfile
+    lines = open(os.path.join(GOLD, 'qn_demote_40000.fastq'), 'rb').read().split(b'\n')
+    names = lines[0:-1:4]
+    assert len(names) == 45000 and all(n[:1] == b'@' for n in names)
+    fields = [n[1:].split(b':') for n in names]
+    assert all(len(f) == 5 and all(x.isdigit() and len(x) <= 8 for x in f) for f in fields)
+    T = (10000, 20000, 40000, 44999)
+    distinct = [[len(set(f[c] for f in fields[:t + 1])) for t in T] for c in range(5)]
+    assert distinct[0] == [1000, 2000, 4200, 4200]          # integers, by the 40 000 checkpoint alone
+    assert distinct[1] == [1000, 2000, 4000, 4000]          # stays a mapping: 4000 is not > 4000
+    assert distinct[2] == [1000, 2000, 4000, 4500]          # integers, by the final check alone: 4500 > 44 999 // 10
+    assert distinct[3] == [1000, 2000, 4000, 4499]          # stays a mapping: 4499 is not > 4499
+    assert [t // 10 for t in T] == [1000, 2000, 4000, 4499] and distinct[4][-1] <= 255
+    for c in range(4):
+        values = [int(x) for x in set(f[c] for f in fields)]
+        assert max(values) - min(values) > 65535 and all((v - 7) % 17 == 0 for v in values)
+    with tarfile.open(os.path.join(GOLD, 'qn_demote_40000.uQ')) as tar:
+        cols = json.load(tar.extractfile('config.json'))['QNAME_columns']
+    assert [(c['format'], c['dtype']) for c in cols] == [('integers', 'uint32'), ('mapping', 'uint16'), ('integers', 'uint32'),
+                                                         ('mapping', 'uint16'), ('integers', 'uint8')]
+    for c, n in ((1, 4000), (3, 4499)):
+        assert len(cols[c]['map']) == n and all(isinstance(v, str) for v in cols[c]['map']) and cols[c]['map'] == sorted(cols[c]['map'])
 
 
 @pytest.mark.parametrize('name', REFUSED)
