@@ -405,7 +405,8 @@ int uq_encode_u32_columns(uq_ctx* ctx, const uint32_t* d_vals, uint64_t vals_pit
  * (uq.py:1010-1026) and its four prints per read (uq.py:1042-1045).  Inputs: the fixed-pitch text and
  * lengths uq_unpack produced, and the QNAME columns (device arrays, one value per read, little-endian
  * unsigned of itemsize[c] bytes).  Integer columns print str(value + add[c]) (add = 'min' when the
- * column has an offset); mapping columns copy string number `value` of a flattened table
+ * column has an offset, any int64): exact wherever value + add[c] lies in [-2^63, 2^64), at every itemsize -- the
+ * caller keeps other columns (an offset beyond int64, sums from 2^64 on) away from the device; mapping columns copy string number `value` of a flattened table
  * (h_d_map_chars[c], h_d_map_offs[c][nmap + 1]; both NULL for integer columns) and pass nmap in add[c] (0 = not
  * given): a value >= nmap then reads the last string, never beyond the table -- uq_check_index_range tells the caller.
  * Record = prefix + fields joined by separators[c] + suffix '\n' SEQ '\n' '+' '\n' QUAL '\n'.

@@ -288,6 +288,10 @@ def cases():
         i % 50 - 25, 100000 + 37000 * i, 5000000000 * (i % 300) + 7 * i, 1000 + i % 90, [5, 70000, 12345678, 31][i % 4]))
     yield 'qn_u4_u8_negative', wide, RAW, False
     yield 'qn_u4_u8_sort_qname_raw_stable', wide, ['--sort', 'QNAME', '--raw', 'QNAME', '--pattern', '0.1', '3.2'], True
+    #     a uint64 column WITH an offset and a negative `min` (one field from -25 to beyond 2**32 in growing steps: stored 0 prints -25), next to a
+    #     20-digit field whose leading digit varies (no prefix swallows it): its `min`, 10**19, is beyond int64, and its larger values beyond 2**64
+    yield 'qn_u8_offset_negative', rename(synth.fastq(S + 34, 300, 24), lambda i: b'@s:%d:%d' % (
+        -25 + 50000 * i * i + 7 * i, (1 + i % 2) * 10 ** 19 + 12345 * i)), RAW, False
     # 20. the checkpoints of uq.py:586-602 at 22 000 reads: column 1 is a mapping at read 10 000 (900 values) and integers at 20 000;
     #     column 2 integers at once; column 3 two strings; column 4 three far-apart numbers until read 21 000, then one per read -- still a
     #     mapping at the last check (1 002 values <= 2 199), stored as uint16 codes of strings

@@ -24,7 +24,7 @@ struct EmitGeom {
     uint32_t prefix_len, suffix_len, ncols, dna_max;
     const void* col[EM_MAXCOLS];          // device column arrays (little-endian unsigned, itemsize bytes)
     uint32_t itemsize[EM_MAXCOLS];
-    int64_t add[EM_MAXCOLS];              // value added to an integer column ('min' when offset, uq.py:1019)
+    int64_t add[EM_MAXCOLS];              // value added to an integer column ('min' when offset, uq.py:1019); mapping columns: the table's length
     const uint8_t* map_chars[EM_MAXCOLS]; // mapping columns: flattened strings; null for integer columns
     const uint32_t* map_offs[EM_MAXCOLS]; // and their offsets [nmap + 1]
 };
@@ -63,10 +63,11 @@ __device__ __forceinline__ uint32_t field_from_raw(const EmitGeom& g, uint32_t c
         mag = 0; neg = false;
         return mo[raw + 1] - moff;
     }
-    const int64_t v = (int64_t)raw + g.add[c];      // str(row[i] + min): columns narrower than 64 bit never wrap here
-    neg = v < 0 && g.itemsize[c] < 8;               // a uint64 column without offset prints as unsigned
-    mag = neg ? (uint64_t)(-v) : (uint64_t)v;
-    if (g.itemsize[c] == 8 && g.add[c] == 0) { mag = raw; neg = false; }
+    // str(row[i] + min), exact wherever raw + add lies in [-2^63, 2^64): raw is unsigned at every width (8 bytes included), add any
+    // int64 -- negated as an unsigned number, which INT64_MIN survives
+    const uint64_t ua = (uint64_t)g.add[c], na = 0 - ua;
+    neg = g.add[c] < 0 && raw < na;
+    mag = neg ? na - raw : raw + ua;
     moff = 0;
     return ndigits_u64(mag) + (neg ? 1u : 0u);
 }

@@ -577,7 +577,10 @@ def _emit_params(ctx, config, column_tensors):
     d_cols = (C.c_void_p * 32)(); d_chars = (C.c_void_p * 32)(); d_offs = (C.c_void_p * 32)()
     for i, c in enumerate(cols):
         p.itemsize[i] = column_tensors[i].element_size()
-        p.add[i] = int(c['min']) if (c['format'] != 'mapping' and c.get('offset')) else 0
+        add = int(c['min']) if (c['format'] != 'mapping' and c.get('offset')) else 0
+        if not -2 ** 63 <= add < 2 ** 63:                          # (ctypes would wrap it silently; Session.device_text_possible keeps such files on the host path)
+            raise ValueError('QNAME column %d: the offset %d does not fit the int64 the device adds' % (i + 1, add))
+        p.add[i] = add
         d_cols[i] = column_tensors[i].data_ptr()
         if c['format'] == 'mapping':
             strs = [s.encode('latin-1') for s in c['map']]
@@ -591,23 +594,26 @@ def _emit_params(ctx, config, column_tensors):
     return p, d_cols, d_chars, d_offs, keep
 
 
-def emit_fastq(ctx, config, column_tensors, seq, qual, ln, nreads):
+def emit_fastq(ctx, config, column_tensors, seq, qual, ln, nreads, size_only=False):
     """Device-side FASTQ text: returns a uint8 tensor with the whole decoded file.
-    `column_tensors`: one device tensor per QNAME column (values per read, the column's dtype)."""
+    `column_tensors`: one device tensor per QNAME column (values per read, the column's dtype).
+    size_only: the size pass alone -- returns the text's length in bytes, writes nothing."""
     t = ctx.torch
     p, d_cols, d_chars, d_offs, keep = _emit_params(ctx, config, column_tensors)
     offsets = t.empty(nreads + 1, dtype=t.int64, device=ctx.device)
     total = C.c_uint64()
     call('uq_emit_fastq', ctx.h, C.byref(p), d_cols, d_chars, d_offs, _p(seq), _p(qual), _p(ln), nreads, _p(offsets), None, 0, C.byref(total))
+    if size_only: return total.value
     out = t.empty(total.value, dtype=t.uint8, device=ctx.device)
     call('uq_emit_fastq', ctx.h, C.byref(p), d_cols, d_chars, d_offs, _p(seq), _p(qual), _p(ln), nreads, _p(offsets), _p(out), total.value, C.byref(total))
     del keep
     return out
 
 
-def decode_fastq(ctx, config, column_tensors, dna, qual, nreads):
+def decode_fastq(ctx, config, column_tensors, dna, qual, nreads, size_only=False):
     """Packed DNA / QUAL tables + QNAME columns -> the FASTQ text (uint8 device tensor), in one pass over the rows
-    (uq_decode_fastq).  Returns (text, bad): bad = lowest row without a length sentinel, or None."""
+    (uq_decode_fastq).  Returns (text, bad): bad = lowest row without a length sentinel, or None.
+    size_only: the first call alone (lengths, record sizes) -- returns (the text's length in bytes, bad), writes no text."""
     t = ctx.torch
     p, d_cols, d_chars, d_offs, keep = _emit_params(ctx, config, column_tensors)
     up = make_unpack_params(config)
@@ -618,6 +624,7 @@ def decode_fastq(ctx, config, column_tensors, dna, qual, nreads):
     args = (ctx.h, C.byref(p), C.byref(up), d_cols, d_chars, d_offs, _p(dna), _p(qual), nreads, _p(ln) if up.variable else None, _p(offsets), _p(d_bad))
     call('uq_decode_fastq', *args, None, 0, C.byref(total), C.byref(bad))
     if bad.value != 2 ** 64 - 1: return None, int(bad.value)
+    if size_only: return total.value, None
     out = t.empty(total.value, dtype=t.uint8, device=ctx.device)
     call('uq_decode_fastq', *args, _p(out), total.value, C.byref(total), C.byref(bad))
     del keep

@@ -917,6 +917,13 @@ class Session:
 
     @staticmethod
     def device_text_possible(config):
+        """Can the device kernels write this file's QNAME lines?  At most 32 columns, prefix and suffix of at most 256 bytes, and integer
+        columns they print exactly: stored value + offset inside [-2**63, 2**64), the offset itself an int64.  Other files take
+        qname.decode_names (Python integers)."""
+        for c in config['QNAME_columns']:
+            if c['format'] == 'mapping': continue
+            if c.get('offset') and not -2 ** 63 <= int(c['min']) < 2 ** 63: return False
+            if int(c.get('max', 0)) >= 2 ** 64: return False
         return len(config['QNAME_columns']) <= 32 and len(config['QNAME_prefix']) <= 256 and len(config['QNAME_suffix']) <= 256
 
     def decode_text(self, config, DNA, QUAL, d_cols):
