@@ -111,8 +111,10 @@ int uq_stats_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_lin
  * one collective per statistics exchange. */
 int uq_stats_export(uq_ctx* ctx, const uq_stats* d_stats, uint32_t rank, uint32_t world, uint64_t read_offset, int64_t* d_words);
 int uq_stats_import(uq_ctx* ctx, const int64_t* d_words, uint32_t world, uq_stats* d_stats);
-/* First occurrence of each base byte: d_first[b] = min over pairs of (read_index << 20 | position),
- * or UQ_NONE.  Only needed to order N-trick candidates as the reference's dict does (uq.py:480). */
+/* First occurrence of each base byte: d_first[b] = min over pairs of (read_index << 32 | position),
+ * or UQ_NONE, read_index = read_index_base + the read's number among [first_read, first_read + nreads): exact order
+ * for every read length a uint32 holds and read numbers below 2^32 (as everywhere in this ABI); shards combine
+ * with MIN.  Only needed to order N-trick candidates as the reference's dict does (uq.py:480). */
 int uq_first_occurrence(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start,
                         uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uint64_t* d_first /*[256], pre-set to UQ_NONE*/);
 

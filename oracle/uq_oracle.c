@@ -27,7 +27,7 @@ uint64_t uqo_index_lines(const uint8_t* buf, uint64_t nbytes, uint64_t* line_sta
 }
 
 /* uq.py:366-375, 382, 388, 415-425: counts[base*256+qual], length range, first bad records,
- * first_seen[base] = (read << 20 | pos) of the first occurrence. */
+ * first_seen[base] = (read << 32 | pos) of the first occurrence (pos is a uint32, as the lengths are). */
 void uqo_stats(const uint8_t* buf, const uint64_t* ls, uint64_t first, uint64_t n, uint64_t* counts /*65536*/,
                uint64_t* first_seen /*256*/, uint32_t* len_min, uint32_t* len_max, uint32_t* max_record_bytes,
                uint64_t* bad_plus, uint64_t* bad_len) {
@@ -44,7 +44,7 @@ void uqo_stats(const uint8_t* buf, const uint64_t* ls, uint64_t first, uint64_t 
         for (uint32_t j = 0; j < Lc; ++j) {
             uint8_t b = buf[s + j], c = buf[q + j];
             counts[(uint32_t)b * 256 + c] += 1;
-            uint64_t key = ((first + r) << 20) | (j & 0xFFFFFu);
+            uint64_t key = ((first + r) << 32) | j;
             if (first_seen && key < first_seen[b]) first_seen[b] = key;
         }
     }

@@ -31,6 +31,12 @@ class FakeIO:
         os.pwrite(fd, tensor.numpy().tobytes(), offset)
 
 
+def _unsigned(index):
+    """The key's bytes are unsigned at every width, 8 bytes included (include/uqhip.h: index_itemsize in {1, 2, 4, 8})."""
+    a = index.numpy()
+    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]).astype(np.uint64)
+
+
 def _npy(a):
     f = io.BytesIO(); np.save(f, a); return f.getvalue()
 
@@ -39,15 +45,11 @@ class FakeOps:
     @staticmethod
     def gather_rows(ctx, table, nrows, cols, index):
         t = table.numpy().reshape(nrows, cols)
-        idx = index.numpy().astype(np.int64)
-        if index.dtype != torch.uint8: idx &= (1 << (8 * index.element_size())) - 1      # the key's bytes are unsigned
-        return torch.from_numpy(np.ascontiguousarray(t[idx]).reshape(-1))
+        return torch.from_numpy(np.ascontiguousarray(t[_unsigned(index).astype(np.int64)]).reshape(-1))
 
     @staticmethod
     def check_index_range(ctx, index, limit):
-        idx = index.numpy().astype(np.int64)
-        if index.dtype != torch.uint8: idx &= (1 << (8 * index.element_size())) - 1
-        bad = np.flatnonzero(idx >= limit)
+        bad = np.flatnonzero(_unsigned(index) >= np.uint64(limit))
         return int(bad[0]) if len(bad) else None
 
     @staticmethod

@@ -2,7 +2,8 @@
 uq_unique_rows, uq_prefix_distinct, uq_narrow, uq_encode_int), following the contracts in include/uqhip.h.
 TEST INFRASTRUCTURE ONLY: lets the CPU suite exercise the host-side decision logic of qname_device (the
 closed form of the reference's sequential QNAME loop) against the oracle without a GPU.  The kernels
-themselves are checked on the GPU by tests/test_gpu_qname.py."""
+themselves are checked on the GPU by tests/test_gpu_qname.py (inside whole analyses) and, output for output against the
+functions below, by tests/test_gpu_helpers_exact.py."""
 import types
 
 import numpy as np

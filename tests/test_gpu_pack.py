@@ -320,6 +320,11 @@ def test_pack_tiles_sized_from_the_average_record(ctx, fused):
     st = ops.stats_new(ctx)
     ops.stats_accumulate(ctx, st, d_buf, ls, 0, n)
     hs = ops.stats_fetch(ctx, st)
+    hls = oracle_c.index_lines(host)
+    ref = oracle_c.stats(host, hls, 0, n)          # the oversize tiles are counted straight from HBM: held to the oracle before they serve as the truth below
+    assert np.array_equal(hs.counts, ref['counts'])
+    assert (hs.len_min, hs.len_max, hs.max_record_bytes) == (ref['len_min'], ref['len_max'], ref['max_record_bytes'])
+    assert (hs.bad_plus, hs.bad_len) == (ref['bad_plus'], ref['bad_len']) == (None, None)
     d = _decide_from_stats(hs)
     p = ops.make_pack_params(d['bases'], d['qualities'], d['N_qual'], d['bits_per_base'], d['bits_per_quality'], d['variable_read_lengths'],
                              d['dna_bytes_per_row'], d['quality_bytes_per_row'], d['dna_max'], hs.max_record_bytes,

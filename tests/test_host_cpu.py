@@ -249,3 +249,39 @@ def test_isa_scan_reads_a_kernel_file():
     r = subprocess.run([sys.executable, os.path.join(repo, 'tools', 'isa_scan.py'), 'scan.hip', '--all'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert 'scan_tile_kernel' in r.stdout and 'vgpr' in r.stdout and 'lwl' in r.stdout
+
+
+def test_sharded_first_seen_keeps_unsigned_key_order_across_ranks():
+    """ShardedSession.first_seen reduces every rank's uq_first_occurrence table with MIN.  The keys are unsigned 64-bit (read << 32 |
+    position): from file-wide read 2^31 on they pass 2^63, and must still be kept, and ordered, as unsigned numbers."""
+    from uq_amd.dist_encode import ShardedSession
+    NONE = (1 << 64) - 1
+    mine, other = [NONE] * 256, [NONE] * 256
+    mine[ord('A')], other[ord('A')] = 5, ((1 << 31) + 9) << 32                   # an early rank wins
+    mine[ord('C')], other[ord('C')] = (((1 << 31) + 2) << 32) | 7, (((1 << 31) + 2) << 32) | 3    # both beyond 2^63
+    mine[ord('G')] = ((1 << 32) - 1) << 32 | 0xFFFFFFFE                          # the last read the ABI numbers, seen by one rank only
+    other[ord('T')] = 1 << 63
+
+    def first_seen_of(table, peer):
+        """first_seen() of a rank whose kernel returned `table`; `peer` = what the other rank put into the MIN (None: a group of one)."""
+        class Ops:
+            @staticmethod
+            def first_occurrence(ctx, buf, ls, first, n, index_base=0):
+                return np.array(table, dtype=np.uint64)
+
+        class Group:
+            sent = None
+
+            def reduce(self, values, op):
+                assert op == 'min' and all(-(1 << 63) <= v < (1 << 63) for v in values)      # what a signed 64-bit collective takes
+                Group.sent = list(values)
+                return values if peer is None else [min(a, b) for a, b in zip(values, peer)]
+
+        s = ShardedSession.__new__(ShardedSession)
+        s.ops, s.ctx, s.d_buf, s._d_ls, s.total, s.read_offset, s.shard = Ops, None, None, object(), 3, 1 << 31, Group()
+        return s.first_seen(), Group.sent
+
+    alone, sent = first_seen_of(other, None)
+    assert alone.dtype == np.uint64 and alone.tolist() == other                  # nothing is clamped, UQ_NONE stays UQ_NONE
+    both, _ = first_seen_of(mine, sent)
+    assert both.tolist() == [min(a, b) for a, b in zip(mine, other)]

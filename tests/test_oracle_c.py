@@ -45,3 +45,26 @@ def test_c_patterns_match_numpy():
         for pat in O.PATTERNS:
             payload = np.frombuffer(O.write_pattern(T, pat), dtype=np.uint8)[-R * C:]
             assert np.array_equal(payload, oracle_c.pattern(T, PATTERN_IDS[pat])), (R, C, pat)
+
+
+def test_c_first_seen_orders_a_read_beyond_2_pow_20_bases():
+    """first_seen sorts the bases as a scan of the lines meets them, at any read length: in a read of 2^20 + 64 bases X appears at
+    position 6 and Y at 2^20 + 5, both N-trick candidates with a shared quality, so the order decides their N_qual codes
+    (oracle_c against the Python restatement, O.pass1 -> O.decide)."""
+    import stats_inputs as SI
+    recs = SI.long_read_records()
+    host = SI.fastq(recs)
+    ls = oracle_c.index_lines(host)
+    st = oracle_c.stats(host, ls, 0, len(recs))
+    order, absent = SI.order_of_keys(st['first_seen'])
+    want = SI.first_appearance(recs)
+    assert [chr(b) for b in want] == ['A', 'X', 'Y', 'C', 'G', 'T']
+    assert order == want and absent == set(range(256)) - set(want)
+    p1 = O.pass1(O.read_lines(host.tobytes()))
+    assert [ord(b) for b in p1['static_qualities']] == want
+    d = O.decide(p1['static_qualities'], p1['dna_min'], p1['dna_max'])
+    assert len(d['N_qual']) == 2 and d['N_qual']['X'] < d['N_qual']['Y']
+    dc = O.decide(O.histogram_to_static_qualities(st['counts'], st['first_seen']), st['len_min'], st['len_max'])
+    assert dc['N_qual'] == d['N_qual']
+    from uq_amd import analysis
+    assert analysis.decide_from_counts(st['counts'], st['len_min'], st['len_max'], first_seen=st['first_seen'])['N_qual'] == d['N_qual']

@@ -345,6 +345,8 @@ __global__ void stats_init_kernel(uq_stats* st) {
 }
 
 // First occurrence of every base byte (ordering of N-trick candidates, uq.py:480 under pypy/py3).
+// key = read << 32 | position: a read's length is a uint32 here (L below), so the position never reaches the read
+// number's bits and keys order exactly as the reference's scan meets the bases, whatever the read length.
 __global__ __launch_bounds__(256) void first_occurrence_kernel(const uint8_t* __restrict__ buf,
                                                                const uint64_t* __restrict__ ls, uint64_t first,
                                                                uint64_t n, uint64_t index_base, uint64_t* __restrict__ out) {
@@ -360,7 +362,7 @@ __global__ __launch_bounds__(256) void first_occurrence_kernel(const uint8_t* __
         const uint32_t L = (uint32_t)(e1 - s - 1);
         for (uint32_t j = lane; j < L; j += 64) {
             uint32_t b = buf[s + j];
-            unsigned long long key = ((index_base + r) << 20) | (j & 0xFFFFFu);
+            const unsigned long long key = ((index_base + r) << 32) | j;
             if (key < seen[b]) atomicMin(&seen[b], key);
         }
     }

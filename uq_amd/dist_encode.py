@@ -158,9 +158,10 @@ class ShardedSession(Session):
     def first_seen(self):
         fs = self.ops.first_occurrence(self.ctx, self.d_buf, self.d_ls, 0, self.total, index_base=self.read_offset) if self.total \
             else np.full(256, np.iinfo(np.uint64).max, dtype=np.uint64)
-        big = (1 << 63) - 1
-        red = self.shard.reduce([min(int(v), big) for v in fs], 'min')
-        return np.array([np.iinfo(np.uint64).max if v == big else v for v in red], dtype=np.uint64)
+        # the keys are unsigned (read << 32 | position: from file-wide read 2^31 on they pass 2^63) and the collective takes signed
+        # numbers: shifted by 2^63 they keep their order, and UQ_NONE stays the largest
+        red = self.shard.reduce([int(v) - (1 << 63) for v in fs], 'min')
+        return np.array([v + (1 << 63) for v in red], dtype=np.uint64)
 
     def reads_in_file(self):
         return self.total_reads

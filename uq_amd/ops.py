@@ -136,6 +136,20 @@ def stats_fetch(ctx, d_stats):
     return HostStats(raw[0])
 
 
+def stats_export(ctx, d_stats, rank, world, read_offset=0):
+    """A device uq_stats as ONE summable buffer (uq_stats_export): int64[65536 + 6 * world] on the device, this rank's scalars in its own
+    six slots (bad records made file-wide with read_offset), zeros in the others."""
+    t = ctx.torch
+    words = t.empty(65536 + 6 * world, dtype=t.int64, device=ctx.device)
+    call('uq_stats_export', ctx.h, _p(d_stats), int(rank), int(world), int(read_offset), _p(words))
+    return words
+
+
+def stats_import(ctx, words, world, d_stats):
+    """The SUM of every rank's stats_export folded back into d_stats (uq_stats_import)."""
+    call('uq_stats_import', ctx.h, _p(words), int(world), _p(d_stats))
+
+
 def first_occurrence(ctx, buf, line_start, first_read, nreads, index_base=0):
     t = ctx.torch
     d = t.full((256,), -1, dtype=t.int64, device=ctx.device)
