@@ -118,6 +118,28 @@ int uq_stats_import(uq_ctx* ctx, const int64_t* d_words, uint32_t world, uq_stat
 int uq_first_occurrence(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start,
                         uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uint64_t* d_first /*[256], pre-set to UQ_NONE*/);
 
+/* ---- the record fingerprint `uqfp1` (an extension: the reference cannot tell whether a container gives its FASTQ back; DESIGN.md
+ * section 19).  Nine u64 sums over records, all arithmetic mod 2^64.  K = 0x9E3779B97F4A7C15;
+ *   mix(x):  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *   line hash LH(tag, b) of a line b[0, L) without its '\n':  w_k = the little-endian u64 of b[8k, 8k + 8), zero-padded, k in [0, ceil(L / 8));
+ *       acc = SUM_k mix(w_k + K (k + 1))  (0 for an empty line);  LH = mix(acc + K L + tag)
+ *   record r (global index, 0-based) with lines q, s, p, u:  hq = LH(1, q), hs = LH(2, s), hu = LH(4, u);
+ *       pair = mix(hs + mix(hu)),  rec = mix(hq + pair),  ord = mix(rec + K (r + 1))
+ * reads; bases = SUM len(s); plus_text = the records whose line 3 is not exactly "+" (line 3 enters nothing else: the format does not store
+ * it); qname = SUM hq, dna = SUM hs, qual = SUM hu, pairs = SUM pair, records = SUM rec, ordered = SUM ord.  Two texts with equal `ordered`
+ * (and reads, bases) hold the same reads in the same order, with equal `records` the same reads as a multiset; the other sums say which
+ * line class differs.  The sums commute: pieces and shards add.  NOT cryptographic: it catches accidents, not adversaries.
+ * uq_fingerprint_init zeroes *d_fp (device, 8-byte aligned).  uq_fingerprint_accumulate ADDS the records [first_read, first_read + nreads)
+ * of d_buf (any alignment; d_line_start as uq_index_lines writes it; lines shorter than 2^32 bytes) into *d_fp, record first_read + i with the
+ * global index read_index_base + i (uq_first_occurrence's convention): one read of the stream, nothing written but the nine sums; queued on
+ * the context's stream.  uq_fingerprint_host: the same, sequentially, on host memory (ADDS into *h_fp; needs no GPU). */
+typedef struct uq_fingerprint { uint64_t reads, bases, plus_text, qname, dna, qual, pairs, records, ordered; } uq_fingerprint;
+int uq_fingerprint_init(uq_ctx* ctx, uq_fingerprint* d_fp);
+int uq_fingerprint_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start,
+                              uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uq_fingerprint* d_fp);
+int uq_fingerprint_host(const uint8_t* h_buf, const uint64_t* h_line_start,
+                        uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uq_fingerprint* h_fp);
+
 /* ---- a3 / a4: the per-read packers.  Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

@@ -74,6 +74,10 @@ class BgzfPart(C.Structure):
                 ('nbytes', C.c_uint64)]
 
 
+class Fingerprint(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('reads', 'bases', 'plus_text', 'qname', 'dna', 'qual', 'pairs', 'records', 'ordered')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -113,6 +117,9 @@ SIGNATURES = {
     'uq_stats_export': [_vp, _vp, _u32, _u32, _u64, _vp],
     'uq_stats_import': [_vp, _vp, _u32, _vp],
     'uq_first_occurrence': [_vp, _vp, _vp, _u64, _u64, _u64, _vp],
+    'uq_fingerprint_init': [_vp, _vp],
+    'uq_fingerprint_accumulate': [_vp, _vp, _vp, _u64, _u64, _u64, _vp],
+    'uq_fingerprint_host': [_vp, _vp, _u64, _u64, _u64, _P(Fingerprint)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

@@ -452,6 +452,10 @@ def main(argv=None):
     if getattr(args, 'gz', False) and not args.decode:
         print('ERROR: the sharded encoder writes a plain .uQ only; --gz is for the single-GPU encoder (python -m uq_amd.uq)')
         return 1
+    if getattr(args, 'verify', False) or getattr(args, 'fingerprint', False):
+        print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
+              "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")
+        return 1
     if args.decode and args.input and os.path.isfile(args.input):
         # the same before any set-up: a gzip container that is not BGZF has no random access, every rank would inflate all of it
         from . import container, ops

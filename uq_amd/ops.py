@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -155,6 +155,69 @@ def first_occurrence(ctx, buf, line_start, first_read, nreads, index_base=0):
     d = t.full((256,), -1, dtype=t.int64, device=ctx.device)
     call('uq_first_occurrence', ctx.h, _p(buf), _p(line_start), first_read, nreads, index_base, _p(d))
     return d.cpu().numpy().view(np.uint64)
+
+
+# ------------------------------------------------------------------ the record fingerprint uqfp1 (include/uqhip.h)
+FINGERPRINT_FIELDS = tuple(k for k, _ in Fingerprint._fields_)
+
+
+def fingerprint_new(ctx):
+    """A zeroed device uq_fingerprint (int64[9]: the bit patterns of its nine u64 sums)."""
+    t = ctx.torch
+    d = t.empty(len(FINGERPRINT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_fingerprint_init', ctx.h, _p(d))
+    return d
+
+
+def fingerprint_accumulate(ctx, d_fp, buf, line_start, first_read, nreads, index_base=0):
+    """Adds the records [first_read, first_read + nreads) of buf into d_fp (queued, nothing read back); record first_read + i counts as the
+    global record index_base + i."""
+    call('uq_fingerprint_accumulate', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), int(index_base), _p(d_fp))
+
+
+def fingerprint_fetch(ctx, d_fp):
+    """The device sums as a dict of Python integers (synchronises)."""
+    return dict(zip(FINGERPRINT_FIELDS, (int(v) for v in ctx.to_numpy(d_fp).view(np.uint64))))
+
+
+def fingerprint(ctx, buf, line_start=None, nreads=None):
+    """The fingerprint of a FASTQ text in HBM (uint8 tensor); without an index it is built here (census + uq_index_lines)."""
+    if line_start is None:
+        nlines = count_lines(ctx, buf) if buf.numel() else 0
+        if nlines % 4: raise ValueError('fingerprint: %d lines are not whole FASTQ records' % nlines)
+        nreads = nlines // 4
+        if nreads: line_start = index_lines(ctx, buf, nlines)
+    d = fingerprint_new(ctx)
+    if nreads: fingerprint_accumulate(ctx, d, buf, line_start, 0, nreads)
+    return fingerprint_fetch(ctx, d)
+
+
+def host_line_starts(data):
+    """What uq_index_lines writes, for host bytes: uint64[lines + 1]."""
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    return np.concatenate(([0], np.flatnonzero(a == 10) + 1)).astype(np.uint64)
+
+
+def fingerprint_host(data, line_start=None, first_read=0, nreads=None, index_base=0):
+    """uq_fingerprint_host: the same sums on the CPU, sequentially, over host bytes (needs no GPU)."""
+    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    ls = np.ascontiguousarray(host_line_starts(a) if line_start is None else line_start, dtype=np.uint64)
+    if nreads is None:
+        if (len(ls) - 1) % 4: raise ValueError('fingerprint: %d lines are not whole FASTQ records' % (len(ls) - 1))
+        nreads = (len(ls) - 1) // 4 - first_read
+    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('fingerprint: records beyond the index')
+    fp = Fingerprint()
+    call('uq_fingerprint_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
+         int(index_base), C.byref(fp))
+    return {k: int(getattr(fp, k)) for k in FINGERPRINT_FIELDS}
+
+
+def fingerprint_json(fp):
+    """The one line --fingerprint prints: counts as numbers, the six sums as 16 hex digits."""
+    import json
+    d = {'uqfp': 1}
+    for i, k in enumerate(FINGERPRINT_FIELDS): d[k] = fp[k] if i < 3 else '%016x' % fp[k]
+    return json.dumps(d)
 
 
 # ------------------------------------------------------------------ pack

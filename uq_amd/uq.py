@@ -80,6 +80,13 @@ def build_parser():
     p.add_argument('--bgzf-level', type=int, default=None, metavar='{1,2}',
                    help='the level of the GPU deflate compressor under --decode --bgzf, --gz and --test --device-compressor: 1 (the default, '
                         'fast) or 2 (more match candidates and a lazy parse: smaller, slower) (extension)')
+    p.add_argument('--verify', action='store_true', default=False,
+                   help='after the container is written: read it back from the disk, decode it on the GPU and compare the record fingerprint of the '
+                        'decoded text with the input\'s -- the same reads in the same order, or with --sort the same reads as a multiset; exit '
+                        'status 1 and a diagnosis if not (extension)')
+    p.add_argument('--fingerprint', action='store_true', default=False,
+                   help='print the record fingerprint (uqfp1, DESIGN.md section 19: not cryptographic) of the input FASTQ as one JSON line and '
+                        'write no container; with --decode: of the decoded text, and write no text (extension)')
     return p
 
 
@@ -109,6 +116,15 @@ def validate_args(args):
                 (getattr(args, 'device_compressor', False) and args.test)):
             error('ERROR: --bgzf-level sets the level of the GPU deflate compressor: use it together with --decode --bgzf, --gz or '
                   '--test --device-compressor')
+    if getattr(args, 'verify', False):
+        if args.decode: error('ERROR: --verify checks the container an encode writes: it does not go with --decode')
+        if args.peek: error('ERROR: --verify reads back the container the encoder writes: --peek writes none')
+        if args.test: error('ERROR: --verify does not go with --test: encode with the parameters --test found, then verify that file')
+        if getattr(args, 'fingerprint', False): error('ERROR: --fingerprint writes no container, so there is nothing for --verify to read back')
+    if getattr(args, 'fingerprint', False):
+        if getattr(args, 'bgzf', False): error('ERROR: --fingerprint writes no text, so there is nothing for --bgzf to compress')
+        if getattr(args, 'gz', False) or args.peek or args.test or args.output:
+            error('ERROR: --fingerprint only reads: it does not go with --gz, --peek, --test or -o')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     return args
 
@@ -232,6 +248,14 @@ class Session:
         ops, ctx, args = self.ops, self.ctx, self.args
         self.d_buf = d_buf
         if not hasattr(self, '_host'): self.path, self._host = None, None
+        if getattr(self, 'index_only', False):           # --fingerprint: the line count and (on first use) the record index, no statistics, no pack
+            self._spec, self._fq, self._d_ls, self.load_path = None, None, None, 'index only'
+            nlines = census.end() if census is not None else ops.count_lines(ctx, d_buf)
+            if nlines % 4 != 0:
+                error('ERROR: The FASTQ file provided contains' + str(nlines) + 'rows, which is not divisible by 4!')
+            if nlines == 0: error('ERROR: empty input')
+            self.total = nlines // 4
+            return
         self._spec, self._fq, self._d_ls, self.load_path = None, None, None, 'multi-pass'
         self._guess_shared = False
         nbytes = int(d_buf.numel())
@@ -782,6 +806,72 @@ class Session:
         self.say('Warming up...')
         self.load(args.input)
         self.encode_loaded()
+        return self.verify() if getattr(args, 'verify', False) else True
+
+    # ------------------------------------------------------------------ the record fingerprint
+    def fingerprint_input(self):
+        """--fingerprint: the input FASTQ (plain, BGZF or other gzip) goes to HBM as for an encode, only the record index is built; one JSON
+        line, no container."""
+        self.index_only = True
+        self.load(self.args.input)
+        fp = self.ops.fingerprint(self.ctx, self.d_buf, self.d_ls, self.total)
+        print(self.ops.fingerprint_json(fp), file=self.out)
+        return fp
+
+    def fingerprint_decoded(self, show=True):
+        """--decode --fingerprint: the fingerprint of the text --decode would write (the text stays in HBM)."""
+        fp = self.ops.fingerprint(self.ctx, self.decode_to_device())
+        if show: print(self.ops.fingerprint_json(fp), file=self.out)
+        return fp
+
+    VERIFY_DECODE_ERRORS = (UqError, RuntimeError, ValueError, IndexError, KeyError, OverflowError, OSError, EOFError)
+
+    def verify(self):
+        """--verify: args.output is reopened through the normal decode path -- the bytes on the disk, a --gz file's members and CRCs included
+        -- decoded to a device tensor and fingerprinted; the result against the fingerprint of the input text, which is still in HBM.  Without a
+        sort `ordered` must be equal, with --sort X `records` (the same reads as a multiset); `reads` and `bases` in both cases.  One line
+        either way, also under --quiet; False = not verified (exit status 1), with what the components say about the cause.  The container
+        stays where it was written."""
+        ops, ctx, args = self.ops, self.ctx, self.args
+        show = lambda *a: print(*a, file=self.out)
+        want = ops.fingerprint(ctx, self.d_buf, self.d_ls, self.total)
+        resorted = args.sort in ('DNA', 'QUAL', 'QNAME')                        # (Q1: any other spelling passes validation and sorts nothing)
+        self.members, self.tables = {}, {}                                      # the tables have been written: their HBM is the decoder's now
+        dargs = argparse.Namespace(**dict(vars(args), input=args.output, output=None, decode=True, bgzf=False, gz=False, verify=False, quiet=True))
+        try:
+            got = Session(dargs, ctx=ctx, out=self.out).fingerprint_decoded(show=False)
+        except self.VERIFY_DECODE_ERRORS as e:
+            show('VERIFY FAILED: %s does not decode: %s' % (args.output, str(e) or type(e).__name__))
+            show('    (one known cause: an N-trick base that took a quality code of its own, SURVEY.md Q9 -- encode such a file with --notricks)')
+            return False
+        self.verify_fingerprints = (want, got)
+        hx = lambda v: '%016x' % v
+        key = 'records' if resorted else 'ordered'
+        if all(want[k] == got[k] for k in ('reads', 'bases', key)):
+            line = 'Verified: %s decodes to the same %d reads %s (%s; records %s)' % (
+                args.output, want['reads'], 'as a multiset, resorted by --sort ' + args.sort if resorted else 'in the same order',
+                key + ' fingerprint equal', hx(got['records']))
+            if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
+            show(line)
+            return True
+        show('VERIFY FAILED: %s does not decode to the reads of %s (%s %s, decoded %s)' % (args.output, args.input, key, hx(want[key]), hx(got[key])))
+        if want['reads'] != got['reads'] or want['bases'] != got['bases']:
+            show('    - the input holds %d reads / %d bases, the decoded text %d / %d' % (want['reads'], want['bases'], got['reads'], got['bases']))
+        elif want['pairs'] == got['pairs'] and want['qname'] != got['qname']:
+            show('    - the sequence and quality lines are verified (pairs %s); the QNAME lines are not reproduced byte for byte:' % hx(got['pairs']))
+            show('      integer QNAME fields are stored as numbers, so leading zeros, a + sign and spaces around them are lost (SURVEY.md Q12)')
+        else:
+            for k, what in (('dna', 'sequence'), ('qual', 'quality')):
+                if want[k] != got[k]: show('    - the %s lines differ (%s %s, decoded %s)' % (what, k, hx(want[k]), hx(got[k])))
+            if want['qname'] != got['qname']: show('    - the QNAME lines differ (qname %s, decoded %s)' % (hx(want['qname']), hx(got['qname'])))
+            if want['dna'] == got['dna'] and want['qual'] == got['qual'] and want['pairs'] != got['pairs']:
+                show('    - every sequence and every quality line is there, but not with its partner (pairs %s, decoded %s)' % (hx(want['pairs']), hx(got['pairs'])))
+            elif want['pairs'] == got['pairs'] and want['qname'] == got['qname'] and want['records'] != got['records']:
+                show('    - every line is there, but the QNAME lines do not sit on their reads (records %s, decoded %s)' % (hx(want['records']), hx(got['records'])))
+        if not resorted and want['records'] == got['records']:
+            show('    - the same reads, reordered: the container stores them in another order than the input')
+        show('    the container stays where it was written.')
+        return False
 
     def encode_loaded(self, write=True):
         """Everything after the FASTQ is in HBM (`load` / `load_device`).  write=False: stop before the container is
@@ -937,17 +1027,39 @@ class Session:
         if bad is not None: error('ERROR: row %d of the DNA table carries no length sentinel; is this a uQ file?' % bad)
         return text
 
-    def decode(self, out=None):
-        from . import qname
-        ctx = self.ctx
-        out = out or sys.stdout
+    def decode_tables(self):
+        """The container of args.input opened and checked, its tables in HBM: (config, DNA, QUAL, QNAME columns)."""
         from . import container
         # a compressed container is verified whole (every member's length and CRC-32) before the first byte of text leaves
         self.source, self.tar_path = container.open_source(self, self.args.input), self.args.input
         if self.source.kind == container.BGZF: self.source.verify_all()
         members, config = self.open_container()
-        DNA, QUAL, d_cols = self.load_tables(members, config)
-        n = DNA[1]
+        return (config,) + tuple(self.load_tables(members, config))
+
+    def host_text_records(self, config, DNA, QUAL, d_cols):
+        """The text of a file whose QNAME lines the device kernels cannot write (device_text_possible), record by record: sequence and quality
+        characters from the device, names from qname.decode_names (Python integers)."""
+        from . import qname
+        ctx, n = self.ctx, DNA[1]
+        seq, qt, ln = self.split_bits(DNA, QUAL, config)
+        dmax = config['dna_max']
+        S = ctx.to_numpy(seq).reshape(n, dmax); Q = ctx.to_numpy(qt).reshape(n, dmax); L = ctx.to_numpy(ln, np.uint32)
+        cols = [ctx.to_numpy(c, np.dtype(cc['dtype'])) for c, cc in zip(d_cols, config['QNAME_columns'])]
+        names = qname.decode_names(config, cols)
+        for r in range(n):
+            l = int(L[r])
+            yield names[r].encode('latin-1') + b'\n' + S[r, :l].tobytes() + b'\n+\n' + Q[r, :l].tobytes() + b'\n'
+
+    def decode_to_device(self):
+        """The decoded FASTQ text as one uint8 device tensor, whichever way the QNAME lines are made: the bytes `decode` writes."""
+        config, DNA, QUAL, d_cols = self.decode_tables()
+        if self.device_text_possible(config): return self.decode_text(config, DNA, QUAL, d_cols)
+        return self.ctx.bytes_to_device(b''.join(self.host_text_records(config, DNA, QUAL, d_cols)))
+
+    def decode(self, out=None):
+        ctx = self.ctx
+        out = out or sys.stdout
+        config, DNA, QUAL, d_cols = self.decode_tables()
         w = out.buffer if hasattr(out, 'buffer') else out
         bgzf = getattr(self.args, 'bgzf', False)
         if self.device_text_possible(config):
@@ -955,15 +1067,8 @@ class Session:
             text = self.decode_text(config, DNA, QUAL, d_cols)
             self.io.device_to_stream(self.ops.bgzf_compress(ctx, text, level=self.bgzf_level) if bgzf else text, w)
         else:
-            seq, qt, ln = self.split_bits(DNA, QUAL, config)
-            dmax = config['dna_max']
-            S = ctx.to_numpy(seq).reshape(n, dmax); Q = ctx.to_numpy(qt).reshape(n, dmax); L = ctx.to_numpy(ln, np.uint32)
-            cols = [ctx.to_numpy(c, np.dtype(cc['dtype'])) for c, cc in zip(d_cols, config['QNAME_columns'])]
-            names = qname.decode_names(config, cols)
             sink = io.BytesIO() if bgzf else w
-            for r in range(n):
-                l = int(L[r])
-                sink.write(names[r].encode('latin-1') + b'\n' + S[r, :l].tobytes() + b'\n+\n' + Q[r, :l].tobytes() + b'\n')
+            for record in self.host_text_records(config, DNA, QUAL, d_cols): sink.write(record)
             if bgzf:
                 # the host-built text goes up to the device and is deflated there like the device text
                 self.io.device_to_stream(self.ops.bgzf_compress(ctx, ctx.bytes_to_device(sink.getvalue()), level=self.bgzf_level), w)
@@ -1030,19 +1135,23 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         validate_args(args)
-        s = Session(args)
+        s = Session(args, out=sys.stdout)
         t_ready = time.perf_counter()                                # interpreter, torch and the device context are up
+        ok = True
         if args.decode:
-            s.decode()
+            if getattr(args, 'fingerprint', False): s.fingerprint_decoded()
+            else: s.decode()
+        elif getattr(args, 'fingerprint', False):
+            s.fingerprint_input()
         else:
-            s.encode()
+            ok = s.encode()
         if os.environ.get('UQ_TIMING'):
             s.ctx.sync()
             print(json.dumps({'uq_timing': 'uq', 'work_s': round(time.perf_counter() - t_ready, 3)}), file=sys.stderr, flush=True)
     except UqError as e:
         print(e)
         return 1
-    return 0
+    return 0 if ok else 1                                            # --verify: 1 = the container was written and does not give the input back
 
 
 if __name__ == '__main__':
