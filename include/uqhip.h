@@ -425,6 +425,41 @@ int uq_encode_u32(uq_ctx* ctx, const uint32_t* d_val, uint64_t n, uint32_t sub, 
 int uq_encode_u32_columns(uq_ctx* ctx, const uint32_t* d_vals, uint64_t vals_pitch, uint64_t n, int ncols, const uint32_t* h_sub,
                           const int* h_itemsize, void* const* h_d_outs);       /* uq_encode_u32 of the first ncols columns of a fused pass, one launch */
 
+/* ---- the host decisions between the passes, in the library (no device, no context: plain host C++).
+ * uq_decide_from_stats = uq.py:448-545 (alphabets ASCII-sorted, the N-trick, the width ladder, bytes per row), the twin of
+ * uq_amd.analysis.decide_from_pairs_py.  The statistics come as h_compact (its first n distinct non-zero counters; n <= UQ_STATS_COMPACT_CAP)
+ * or, when h_compact is NULL, as the dense table h_dense[65536]; the read lengths are passed on their own.  h_first_seen: NULL or
+ * 256 sort keys (lower = the base appeared earlier) that order two or more N-trick candidates; ncand says whether they were needed.
+ * status 1: no base counted. */
+typedef struct uq_decisions {
+    uint32_t status, nbases, nquals, nall, nnq, ncand;
+    uint8_t bases[256], qualities[256], all_bases[256];      /* bases: the DNA alphabet left after the N-trick; all_bases: before it */
+    uint8_t nq_base[256]; int32_t nq_code[256];              /* N_qual, in the order the candidates were taken */
+    int32_t total_quals, bits_per_base, bits_per_quality, variable, dna_max, dna_min, dna_bytes_per_row, quality_bytes_per_row;
+    uint64_t base_tot[256], qual_tot[256];
+} uq_decisions;
+int uq_decide_from_stats(const uq_stats_compact* h_compact, const uint64_t* h_dense, uint32_t len_min, uint32_t len_max, int notricks, int pad,
+                         const uint64_t* h_first_seen, uq_decisions* h_out);
+/* uq_pack_params from the decisions (ops.make_pack_params): code tables from the alphabets (a byte given twice keeps its last index),
+ * n_qual from the nnq (byte, code) pairs. */
+int uq_make_pack_params(const uint8_t* bases, uint32_t nbases, const uint8_t* qualities, uint32_t nquals, const uint8_t* nq_base,
+                        const int32_t* nq_code, uint32_t nnq, int32_t bits_per_base, int32_t bits_per_quality, int32_t variable,
+                        int32_t dna_bytes_per_row, int32_t quality_bytes_per_row, int32_t dna_max, int32_t max_record_bytes,
+                        int32_t avg_record_bytes, uq_pack_params* h_out);
+/* *h_same = 1: a and b describe the same encoding (everything but the two tile-sizing hints). */
+int uq_same_pack_params(const uq_pack_params* a, const uq_pack_params* b, int* h_same);
+/* The column typing of uq.py:586-678 from a fetched uq_qname_fused (uq_amd.qname_device.fused_columns_py is the twin): for n reads,
+ * status 0 = ncols columns typed (all `integers`), 1 = decline (no guess, a flag, another read count or other checkpoints than n's, a
+ * column that stays a mapping of strings), 2 = a column needs the sort-based distinct counts.  Columns are judged in order; the first
+ * that declines or needs the sort decides.  from_mapping[c] = 1: the column kept the format `mapping` through every checkpoint and
+ * became `integers` by its value range (its dtype follows the distinct count, not the range). */
+typedef struct uq_qname_columns {
+    uint32_t status, ncols;
+    uint32_t itemsize[UQ_QF_MAXC], offset[UQ_QF_MAXC], from_mapping[UQ_QF_MAXC];     /* itemsize 1, 2, 4, 8 = uint8 ... uint64 */
+    uint32_t vmin[UQ_QF_MAXC], vmax[UQ_QF_MAXC];
+} uq_qname_columns;
+int uq_qname_fused_columns(const uq_qname_fused* h_q, uint64_t n, uq_qname_columns* h_out);
+
 /* ---- f3: FASTQ text assembled on the device.  Replaces the decoder's exec-compiled convert_qname
  * (uq.py:1010-1026) and its four prints per read (uq.py:1042-1045).  Inputs: the fixed-pitch text and
  * lengths uq_unpack produced, and the QNAME columns (device arrays, one value per read, little-endian

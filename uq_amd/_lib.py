@@ -58,6 +58,25 @@ class QnameFused(C.Structure):
                 ('nreads', C.c_uint64), ('thresholds', C.c_uint64 * 24), ('counts', (C.c_uint64 * 24) * 8)]
 
 
+class StatsCompact(C.Structure):
+    _fields_ = [('n', C.c_uint32), ('len_min', C.c_uint32), ('len_max', C.c_uint32), ('max_record_bytes', C.c_uint32), ('reserved', C.c_uint32),
+                ('pad', C.c_uint32), ('bad_plus', C.c_uint64), ('bad_len', C.c_uint64), ('key', C.c_uint32 * 2048), ('count', C.c_uint64 * 2048)]
+
+
+class Decisions(C.Structure):
+    _fields_ = [('status', C.c_uint32), ('nbases', C.c_uint32), ('nquals', C.c_uint32), ('nall', C.c_uint32), ('nnq', C.c_uint32), ('ncand', C.c_uint32),
+                ('bases', C.c_uint8 * 256), ('qualities', C.c_uint8 * 256), ('all_bases', C.c_uint8 * 256),
+                ('nq_base', C.c_uint8 * 256), ('nq_code', C.c_int32 * 256),
+                ('total_quals', C.c_int32), ('bits_per_base', C.c_int32), ('bits_per_quality', C.c_int32), ('variable', C.c_int32),
+                ('dna_max', C.c_int32), ('dna_min', C.c_int32), ('dna_bytes_per_row', C.c_int32), ('quality_bytes_per_row', C.c_int32),
+                ('base_tot', C.c_uint64 * 256), ('qual_tot', C.c_uint64 * 256)]
+
+
+class QnameColumns(C.Structure):
+    _fields_ = [('status', C.c_uint32), ('ncols', C.c_uint32), ('itemsize', C.c_uint32 * 8), ('offset', C.c_uint32 * 8),
+                ('from_mapping', C.c_uint32 * 8), ('vmin', C.c_uint32 * 8), ('vmax', C.c_uint32 * 8)]
+
+
 class GzipStreamInfo(C.Structure):
     _fields_ = [('chunks', C.c_uint64), ('starts', C.c_uint64), ('rounds', C.c_uint64), ('redecoded', C.c_uint64),
                 ('overflows', C.c_uint64), ('resolve_rounds', C.c_uint64), ('members', C.c_uint64), ('out_bytes', C.c_uint64),
@@ -161,6 +180,10 @@ SIGNATURES = {
     'uq_qname_fused_first_seen': [_vp, _vp, _u64, _u64, _u64, _P(_u32), _P(_u32), _int, _vp],
     'uq_encode_u32': [_vp, _vp, _u64, _u32, _int, _vp],
     'uq_encode_u32_columns': [_vp, _vp, _u64, _u64, _int, _P(_u32), _P(_int), _P(_vp)],
+    'uq_decide_from_stats': [_vp, _vp, _u32, _u32, _int, _int, _vp, _P(Decisions)],
+    'uq_make_pack_params': [C.c_char_p, _u32, C.c_char_p, _u32, C.c_char_p, _P(C.c_int32), _u32] + [C.c_int32] * 8 + [_P(PackParams)],
+    'uq_same_pack_params': [_P(PackParams), _P(PackParams), _P(_int)],
+    'uq_qname_fused_columns': [_P(QnameFused), _u64, _P(QnameColumns)],
     'uq_emit_fastq': [_vp, _P(EmitParams), _P(_vp), _P(_vp), _P(_vp), _vp, _vp, _vp, _u64, _vp, _vp, _u64, _P(_u64)],
     'uq_debug_scribble_lds': [_vp, C.c_uint32],
     'uq_sort_config': [_vp, C.c_int64, _P(_int), _int],

@@ -2,9 +2,18 @@
 widths and row bytes, from the 256 x 256 (base, quality) count matrix the device produced -- or from the list of its non-zero entries.
 
 Mirrors uq.py:448-457 (alphabets, ASCII-sorted), 477-494 (N-trick), 497-516 and 534-545 (widths and
-bytes per row).  Negligible work (<= 65536 counters), so it stays on the host like the reference's.
+bytes per row).  Negligible work (<= 65536 counters), so it stays on the host like the reference's -- but as host C++ in the
+library (uq_decide_from_stats, csrc/decide.hip): the encode step ends on these decisions with the device idle, and the numpy
+set-up of a dozen small arrays cost more than the arithmetic.  `decide_from_pairs_py` is the same in numpy: the twin the
+tests hold the native function to.
 """
+import ctypes as C
+
 import numpy as np
+
+from ._lib import Decisions, StatsCompact, call
+
+_SIGN = np.uint64(1 << 63)
 
 
 def bits_for(n_symbols, pad):
@@ -18,6 +27,38 @@ def bits_for(n_symbols, pad):
     return 8
 
 
+def _order_keys(fs):
+    """first_seen as 256 uint64 sort keys with the order of its values as Python integers (a signed array keeps its sign)."""
+    a = np.asarray(fs)
+    if a.dtype.kind == 'u': return np.ascontiguousarray(a, dtype=np.uint64)
+    return np.ascontiguousarray(a.astype(np.int64).view(np.uint64) ^ _SIGN)
+
+
+def _decide_native(compact, dense, len_min, len_max, notricks, pad, first_seen):
+    """uq_decide_from_stats on a uq_stats_compact (address) or a dense uint64[65536] table (address) -> the dict of decisions."""
+    out = Decisions()
+    args = (compact, dense, int(len_min), int(len_max), 1 if notricks else 0, 1 if pad else 0)
+    call('uq_decide_from_stats', *args, None, C.byref(out))
+    if out.ncand > 1 and first_seen is not None and not out.status:          # only consulted when two or more bases qualify
+        fs = first_seen() if callable(first_seen) else first_seen
+        if fs is not None:
+            keys = _order_keys(fs)
+            call('uq_decide_from_stats', *args, keys.ctypes.data, C.byref(out))
+    if out.status:
+        raise ValueError('no bases counted')
+    all_bases = C.string_at(out.all_bases, out.nall)
+    quals = C.string_at(out.qualities, out.nquals)
+    return {
+        'bases': C.string_at(out.bases, out.nbases).decode('latin-1'), 'qualities': quals.decode('latin-1'),
+        'N_qual': {chr(out.nq_base[i]): out.nq_code[i] for i in range(out.nnq)}, 'total_quals': out.total_quals,
+        'bits_per_base': out.bits_per_base, 'bits_per_quality': out.bits_per_quality,
+        'variable_read_lengths': bool(out.variable), 'dna_max': out.dna_max, 'dna_min': out.dna_min,
+        'dna_bytes_per_row': out.dna_bytes_per_row, 'quality_bytes_per_row': out.quality_bytes_per_row,
+        'base_distribution': {chr(x): out.base_tot[x] for x in all_bases},
+        'qual_distribution': {chr(x): out.qual_tot[x] for x in quals},
+    }
+
+
 def decide_from_counts(counts, len_min, len_max, notricks=False, pad=False, first_seen=None):
     """counts[base][qual] (256 x 256, any integer dtype) -> the encoder's parameters.
 
@@ -25,20 +66,44 @@ def decide_from_counts(counts, len_min, len_max, notricks=False, pad=False, firs
     first occurrence; it orders the N-trick candidates the way the reference's dict iteration does
     (uq.py:480 under pypy / py3: first appearance).  Only consulted when two or more bases qualify.
     """
-    flat = np.asarray(counts).reshape(65536)
-    keys = np.flatnonzero(flat)
-    return decide_from_pairs(keys, flat[keys], len_min, len_max, notricks=notricks, pad=pad, first_seen=first_seen)
+    dense = np.ascontiguousarray(np.asarray(counts).reshape(65536), dtype=np.uint64)
+    return _decide_native(None, dense.ctypes.data, len_min, len_max, notricks, pad, first_seen)
 
 
 def decide_from_stats(hs, notricks=False, pad=False, first_seen=None):
     """The same from a HostStats (ops.stats_fetch): its list of non-zero counters when it holds one, else its dense table."""
+    compact = getattr(hs, 'compact', None)
+    if compact is not None:                                      # the uq_stats_compact as it was fetched
+        return _decide_native(compact.ctypes.data, None, hs.len_min, hs.len_max, notricks, pad, first_seen)
     if getattr(hs, 'nz_keys', None) is not None:
         return decide_from_pairs(hs.nz_keys, hs.nz_counts, hs.len_min, hs.len_max, notricks=notricks, pad=pad, first_seen=first_seen)
     return decide_from_counts(hs.counts, hs.len_min, hs.len_max, notricks=notricks, pad=pad, first_seen=first_seen)
 
 
 def decide_from_pairs(keys, cnts, len_min, len_max, notricks=False, pad=False, first_seen=None):
-    """The decisions from the NON-ZERO counters alone: keys = base * 256 + quality (any order), cnts their counts.  A file uses a
+    """The decisions from the NON-ZERO counters alone: keys = base * 256 + quality (distinct, any order), cnts their counts."""
+    keys = np.asarray(keys, dtype=np.int64); cnts = np.asarray(cnts, dtype=np.int64)
+    if keys.size > 2048:                                         # UQ_STATS_COMPACT_CAP: the dense table
+        dense = np.zeros(65536, dtype=np.uint64)
+        dense[keys] = cnts.astype(np.uint64)
+        return _decide_native(None, dense.ctypes.data, len_min, len_max, notricks, pad, first_seen)
+    sc = StatsCompact()
+    sc.n = keys.size
+    np.frombuffer(sc, dtype=np.uint32, count=keys.size, offset=StatsCompact.key.offset)[:] = keys
+    np.frombuffer(sc, dtype=np.uint64, count=keys.size, offset=StatsCompact.count.offset)[:] = cnts.astype(np.uint64)
+    return _decide_native(C.addressof(sc), None, len_min, len_max, notricks, pad, first_seen)
+
+
+def decide_from_counts_py(counts, len_min, len_max, notricks=False, pad=False, first_seen=None):
+    """decide_from_counts through the numpy twin."""
+    flat = np.asarray(counts).reshape(65536)
+    keys = np.flatnonzero(flat)
+    return decide_from_pairs_py(keys, flat[keys], len_min, len_max, notricks=notricks, pad=pad, first_seen=first_seen)
+
+
+def decide_from_pairs_py(keys, cnts, len_min, len_max, notricks=False, pad=False, first_seen=None):
+    """The numpy twin of uq_decide_from_stats (what this module ran before the decisions moved into the library; the tests compare the two).
+    The decisions from the NON-ZERO counters alone: keys = base * 256 + quality (any order), cnts their counts.  A file uses a
     few hundred of the 65 536 counters; everything below is arithmetic on that list."""
     keys = np.asarray(keys, dtype=np.int64); cnts = np.asarray(cnts, dtype=np.int64)
     live = cnts != 0

@@ -21,7 +21,7 @@ struct uq_ctx {
     const uint8_t* idx_buf; uint64_t idx_nbytes; uint64_t idx_nlines;
     uint32_t* idx_partials; size_t idx_partials_cap;
     uint16_t* idx_bitmap;   // newline bitmap of that buffer: one u16 per 16-byte vector (index.hip)
-    uint64_t* h_pinned;     // small pinned host staging (64 KiB).  Who uses which part (uint64 index): [0, 3200) whatever the running call reads
+    uint64_t* h_pinned;     // small pinned host staging (128 KiB); [8192, 11272) the uq_stats_compact sent by uq_qname_fused_finish's read-back.  Who uses which part (uint64 index): [0, 3200) whatever the running call reads
                             // back (scalars, uq_stats_compact, QNAME reductions); [4096, 5120) the radix sort's digit census; [8000, 8003) the
                             // queued census's line count and flags, which must survive the calls queued behind it (uq_count_lines_wait); [5200, 5520) the
                             // fused QNAME pass's structure (uq_qname_fused_finish -> uq_qname_fused_fetch)
@@ -30,6 +30,15 @@ struct uq_ctx {
     // the queued form of the census (uq_count_lines_end_async): the line count stays on the device for the kernels queued behind it
     unsigned long long* d_async;           // [0] line count  [1] line_start capacity exceeded
     const uint8_t* async_buf; uint64_t async_nbytes; bool async_read;
+    bool census_begun; uint64_t census_nb;  // uq_count_lines_begin has cleared d_async for a census of census_nb tiles: uq_count_lines_end_async queues no clear (index.hip)
+    uint32_t* qf_first;                    // the first-occurrence tables of uq_qname_fused_finish: all 0xFF between calls (qname_fused.hip)
+    void* qf_lay; bool qf_lay_dirty;       // the sample's layout reductions (qname_fused.hip): at their initial values between two guesses, like qf_first
+    bool qf_dirty;                         // ... unless a call failed between the kernel that fills them and the one that restores them: refill
+    // the epilogue behind a queued pack + QNAME kernel (qname_fused.hip): uq_pack_stats_qname_async notes its uq_stats (pk_stats, for the
+    // structure pk_q); uq_qname_fused_finish of that structure compacts them in its epilogue launch into d_compact and sends them, with the
+    // census's words and the structure, in ONE read-back; stats_sent = the uq_stats whose list is on its way to h_pinned[8192 ...)
+    const void* pk_stats; const void* pk_q; const void* stats_sent;
+    uq_stats_compact* d_compact;
     const void* qf_sent;                   // the uq_qname_fused whose read-back uq_qname_fused_finish has queued ([5200, 5520) of h_pinned)
     // the row sort's round 0 (uq_sort_config / uq_sort_counters): tables of msd_min_rows rows and more take the MSD partition (0 = the default
     // threshold, < 0 = never); msd_levels > 0: the digits of its levels instead of the automatic plan; how many sorts went which way
@@ -37,7 +46,7 @@ struct uq_ctx {
     unsigned long long n_msd_rounds, n_lsd_rounds;
     // per-context caches of what used to be function statics (a second context on another device, or on another thread, must not share them):
     // register counts of the pack kernels by kernel pointer (the persistent grid is sized from them), and whether this context's device has had
-    // qf_wide_kernel's dynamic LDS limit raised
+    // qf_epilogue_kernel's dynamic LDS limit raised
     const void* kreg_key[8]; int kreg_val[8]; int kreg_n;
     bool qf_attr_set;
 };
@@ -68,6 +77,9 @@ void uq_set_error(const char* fmt, ...);
 // copy of a few bytes was seen to wait 0.2 - 0.6 ms for its turn, an ordinary one-workgroup kernel is dispatched at once.
 int uq_read_back(uq_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);
 int uq_async_read_back(uq_ctx* ctx);        // index.hip: the queued census's results (line count, overflow flags) -> pinned staging
+// index.hip: the same as sources for somebody else's read-back launch (uq_qname_fused_finish); false = nothing to send (sent already, or no census queued).
+// The caller marks them sent with ctx->async_read = true once its launch is queued.
+bool uq_async_sources(uq_ctx* ctx, const uint32_t** d_async, const uint32_t** d_over);
 
 // Scratch: returns a pointer into the context's pool, growing it if needed.  A grow synchronises the
 // stream first (the old pool may still be in use by queued kernels).

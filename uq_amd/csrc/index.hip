@@ -26,6 +26,7 @@ constexpr uint64_t IDX_WAVE_BYTES = 64 * 16 * IDX_LOADS;      // 4096
 constexpr uint64_t IDX_TILE = IDX_WAVE_BYTES * (IDX_THREADS / 64);  // 16384
 constexpr uint64_t IDX_TILE_VECS = IDX_TILE / 16;             // 1024 vectors = 256 bitmap words of 64 bits
 constexpr uint32_t IDX_LIST_CAP = 1024;                       // newline offsets a tile's list slot holds
+constexpr uint32_t IDX_BUCKET = 1024;                         // census tiles per entry of the coarse table the queued census's closing scan starts from
 
 // `abuf` = buf rounded down to 16 bytes, `mis` = buf - abuf.  Stream position of abuf[x] is x - mis.
 // bitmap[vi] = newline mask of vector vi (0 beyond the stream; every vector of every tile is written).
@@ -122,6 +123,57 @@ __global__ __launch_bounds__(IDX_THREADS) void census_list_kernel(const uint4* _
     if (over) atomicOr(overflow, 1u);
 }
 
+// The closing scan of the queued census in TWO launches (the hierarchical scan of scan.hip is four dependent launches of ~5 us each
+// between the census and the pack kernel): census_bucket_kernel leaves one total per IDX_BUCKET tiles; in census_scan_kernel workgroup b
+// sums the bucket totals in front of it, scans its own IDX_BUCKET counts in place, and the last one leaves the line count in
+// d_async[0].  No workgroup reads what another one of its launch writes.  32-bit sums, widened at the end, like uq_scan_exclusive_u32 +
+// widen_total_kernel.  (The bucket totals added up by the census kernel itself, one atomic add a workgroup, made this ONE launch -- and
+// the 0.67 ms census 0.08 ms longer: DESIGN.md section 20.)
+__global__ __launch_bounds__(IDX_THREADS) void census_bucket_kernel(const uint32_t* __restrict__ partials, uint64_t nb, uint32_t* __restrict__ buckets) {
+    __shared__ uint32_t lds[IDX_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * IDX_BUCKET + (uint64_t)threadIdx.x * 4;
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) s += i0 + k < nb ? partials[i0 + k] : 0u;
+    s = wave_sum(s);
+    if (lane_id() == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) buckets[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
+}
+__global__ __launch_bounds__(IDX_THREADS) void census_scan_kernel(uint32_t* __restrict__ partials, uint64_t nb, const uint32_t* __restrict__ buckets,
+                                                                   unsigned long long* __restrict__ d_async) {
+    __shared__ uint32_t lds[IDX_THREADS / 64 + 1];
+    static_assert(IDX_BUCKET == 4 * IDX_THREADS, "four counts a lane");
+    const uint32_t b = blockIdx.x;
+    // every workgroup reads all bucket totals in front of it: nbk^2 / 2 loads over the launch -- 20 k at 10 M reads (203 buckets), 8 M at
+    // 200 M reads (4 100 buckets), still microseconds.  Not a scan for far larger tile counts than a census has (16 MiB of text a bucket).
+    uint32_t s = 0;
+    for (uint32_t i = threadIdx.x; i < b; i += IDX_THREADS) s += buckets[i];
+    s = wave_sum(s);
+    if (lane_id() == 0) lds[threadIdx.x >> 6] = s;
+    __syncthreads();
+    uint32_t base = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < IDX_THREADS / 64; ++i) base += lds[i];
+    __syncthreads();
+    const uint64_t i0 = (uint64_t)b * IDX_BUCKET + (uint64_t)threadIdx.x * 4;
+    uint32_t v[4], sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { v[k] = i0 + k < nb ? partials[i0 + k] : 0u; sum += v[k]; }
+    uint32_t tot;
+    uint32_t run = base + block_exclusive_sum<uint32_t, IDX_THREADS / 64>(sum, lds, tot);
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) { if (i0 + k < nb) partials[i0 + k] = run; run += v[k]; }
+    if (b == gridDim.x - 1 && threadIdx.x == 0) d_async[0] = (unsigned long long)(base + tot);
+}
+
+// what a chunked census starts from, in one launch: the overflow word (behind the list slots) and the queued form's words (d_async) are zero
+__global__ void census_clear_kernel(uint32_t* __restrict__ region, uint32_t nwords, unsigned long long* __restrict__ d_async) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nwords) region[i] = 0;
+    if (i < 8) d_async[i] = 0;
+}
+
 // A wave per tile: line_start[rank + 1] = stream position of the byte after the newline.
 // d_async (the queued form, uq_index_lines_async): the line count is read from d_async[0] -- the census's scan, queued in front,
 // left it there -- and line_start holds `cap` + 1 entries: lines beyond are dropped and d_async[1] is raised.
@@ -190,11 +242,14 @@ int census_buffers(uq_ctx* ctx, uint64_t nb) {
         UQ_CHECK_HIP(hipMalloc((void**)&ctx->idx_partials, (nb + 1) * sizeof(uint32_t)));
         // one buffer serves both forms: nb * 1024 u16 = the bitmap of nb tiles = nb list slots of IDX_LIST_CAP entries
         static_assert(IDX_TILE_VECS == IDX_LIST_CAP, "bitmap words and list entries per tile share one allocation");
-        UQ_CHECK_HIP(hipMalloc((void**)&ctx->idx_bitmap, nb * IDX_TILE_VECS * sizeof(uint16_t) + 16));
+        // behind the slots: 16 bytes whose first word is the overflow flag, then the bucket totals of the queued census's scan (census_buckets)
+        UQ_CHECK_HIP(hipMalloc((void**)&ctx->idx_bitmap, nb * IDX_TILE_VECS * sizeof(uint16_t) + 16 + ((nb + IDX_BUCKET - 1) / IDX_BUCKET) * sizeof(uint32_t)));
         ctx->idx_partials_cap = nb + 1;
     }
     return 0;
 }
+
+uint32_t* census_buckets(uq_ctx* ctx, uint64_t nb) { return (uint32_t*)(ctx->idx_bitmap + nb * IDX_TILE_VECS) + 4; }
 
 int run_count(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, uint64_t* nblocks_out, bool list_form) {
     const uint32_t mis = (uint32_t)((uintptr_t)d_buf & 15);
@@ -202,6 +257,7 @@ int run_count(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, uint64_t* nblo
     const uint64_t nb = (nvec * 16 + IDX_TILE - 1) / IDX_TILE;
     UQ_REQUIRE(nb <= 0x7fffffffu, "uq_count_lines: buffer too large for one launch");
     ctx->async_buf = nullptr;                              // the lists of a queued census (if any) are about to be overwritten: its index-free consumers must refuse
+    ctx->census_begun = false;
     UQ_TRY(census_buffers(ctx, nb));
     if (list_form) {
         uint32_t* d_over = (uint32_t*)(ctx->idx_bitmap + nb * IDX_TILE_VECS);          // the 16 spare bytes behind the slots
@@ -235,6 +291,7 @@ extern "C" int uq_count_lines(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes
 // ---- the census in pieces: a file arrives in HBM chunk by chunk; every chunk's newlines are counted and
 // listed while the next one is still crossing PCIe, so that only the scan of the per-tile counts is left when the last byte lands.
 static int finish_count(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, uint64_t nb, uint64_t* h_nlines) {
+    ctx->census_begun = false;
     void* scr;
     UQ_TRY(uq_scratch(ctx, 256, &scr));
     UQ_TRY(uq_scan_exclusive_u32(ctx, ctx->idx_partials, ctx->idx_partials, nb, (uint64_t*)scr));
@@ -249,6 +306,7 @@ static int finish_count(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, uint
 
 extern "C" int uq_count_lines_begin(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes) {
     UQ_REQUIRE(ctx && (d_buf || nbytes == 0), "uq_count_lines_begin: null argument");
+    ctx->census_begun = false;
     ctx->idx_buf = nullptr;
     ctx->async_buf = nullptr;
     if (nbytes == 0) return 0;
@@ -256,7 +314,12 @@ extern "C" int uq_count_lines_begin(uq_ctx* ctx, const uint8_t* d_buf, uint64_t 
     const uint64_t nb = (((nbytes + mis + 15) / 16) * 16 + IDX_TILE - 1) / IDX_TILE;
     UQ_REQUIRE(nb <= 0x7fffffffu, "uq_count_lines_begin: buffer too large");
     UQ_TRY(census_buffers(ctx, nb));
-    UQ_CHECK_HIP(hipMemsetAsync(ctx->idx_bitmap + nb * IDX_TILE_VECS, 0, 4, ctx->stream));
+    // one clear for everything the chunks and the queued form's consumers raise: the overflow word and d_async.  Here, in front of the
+    // census, it is off the step's critical path (a clear in uq_count_lines_end_async stands between the census and everything queued
+    // behind it).
+    census_clear_kernel<<<1, 64, 0, ctx->stream>>>((uint32_t*)(ctx->idx_bitmap + nb * IDX_TILE_VECS), 4, ctx->d_async);
+    UQ_LAUNCH_CHECK();
+    ctx->census_begun = true; ctx->census_nb = nb;
     return 0;
 }
 
@@ -295,11 +358,23 @@ extern "C" int uq_count_lines_end(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nb
 extern "C" int uq_count_lines_end_async(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes) {
     UQ_REQUIRE(ctx && (d_buf || nbytes == 0), "uq_count_lines_end_async: null argument");
     ctx->idx_buf = nullptr; ctx->async_buf = nullptr; ctx->async_read = false;
-    UQ_CHECK_HIP(hipMemsetAsync(ctx->d_async, 0, 64, ctx->stream));
+    // uq_count_lines_begin of this census has cleared d_async: no clear between the census and the closing scan
+    const bool begun = ctx->census_begun && nbytes != 0;
+    ctx->census_begun = false;
+    if (!begun) UQ_CHECK_HIP(hipMemsetAsync(ctx->d_async, 0, 64, ctx->stream));
     if (nbytes == 0) { ctx->h_pinned[8000] = 0; ctx->h_pinned[8001] = 0; ctx->h_pinned[8002] = 0; ctx->async_buf = d_buf; ctx->async_nbytes = 0; return 0; }
     const uint32_t mis = (uint32_t)((uintptr_t)d_buf & 15);
     const uint64_t nb = (((nbytes + mis + 15) / 16) * 16 + IDX_TILE - 1) / IDX_TILE;
-    UQ_TRY(uq_scan_exclusive_u32(ctx, ctx->idx_partials, ctx->idx_partials, nb, (uint64_t*)ctx->d_async));
+    if (begun && ctx->census_nb == nb) {
+        const uint32_t nbk = (uint32_t)((nb + IDX_BUCKET - 1) / IDX_BUCKET);
+        census_bucket_kernel<<<nbk, IDX_THREADS, 0, ctx->stream>>>(ctx->idx_partials, nb, census_buckets(ctx, nb));
+        UQ_LAUNCH_CHECK();
+        census_scan_kernel<<<nbk, IDX_THREADS, 0, ctx->stream>>>(ctx->idx_partials, nb, census_buckets(ctx, nb), ctx->d_async);
+        UQ_LAUNCH_CHECK();
+    } else {
+        if (begun) UQ_CHECK_HIP(hipMemsetAsync(ctx->d_async, 0, 64, ctx->stream));      // (another buffer's begin: nothing of it is used)
+        UQ_TRY(uq_scan_exclusive_u32(ctx, ctx->idx_partials, ctx->idx_partials, nb, (uint64_t*)ctx->d_async));
+    }
     ctx->async_buf = d_buf; ctx->async_nbytes = nbytes;
     return 0;
 }
@@ -318,14 +393,30 @@ extern "C" int uq_index_lines_async(uq_ctx* ctx, const uint8_t* d_buf, uint64_t 
     return 0;
 }
 
+namespace {
+// d_async[0 .. 1] and the overflow word -> h_pinned[8000 .. 8002], in one launch (uq_read_back's reasons: no copy command)
+__global__ void async_read_back_kernel(const uint32_t* __restrict__ d_async, const uint32_t* __restrict__ over, uint32_t* __restrict__ dst) {
+    const uint32_t t = threadIdx.x;
+    if (t < 4) dst[t] = d_async[t];
+    else if (t == 4) dst[4] = *over;
+}
+}  // namespace
+
 // what uq_count_lines_wait hands out, sent on its way to the host (uq_pack_stats_async queues this behind its kernel: nothing small
 // stands between the index and the pack kernel)
-int uq_async_read_back(uq_ctx* ctx) {
-    if (!ctx->async_buf || ctx->async_nbytes == 0 || ctx->async_read) return 0;
+bool uq_async_sources(uq_ctx* ctx, const uint32_t** d_async, const uint32_t** d_over) {
+    if (!ctx->async_buf || ctx->async_nbytes == 0 || ctx->async_read) return false;
     const uint32_t mis = (uint32_t)((uintptr_t)ctx->async_buf & 15);
     const uint64_t nb = (((ctx->async_nbytes + mis + 15) / 16) * 16 + IDX_TILE - 1) / IDX_TILE;
-    UQ_TRY(uq_read_back(ctx, ctx->h_pinned + 8000, ctx->d_async, 16));
-    UQ_TRY(uq_read_back(ctx, ctx->h_pinned + 8002, ctx->idx_bitmap + nb * IDX_TILE_VECS, 4));
+    *d_async = (const uint32_t*)ctx->d_async; *d_over = (const uint32_t*)(ctx->idx_bitmap + nb * IDX_TILE_VECS);
+    return true;
+}
+
+int uq_async_read_back(uq_ctx* ctx) {
+    const uint32_t *d_async, *d_over;
+    if (!uq_async_sources(ctx, &d_async, &d_over)) return 0;
+    async_read_back_kernel<<<1, 64, 0, ctx->stream>>>(d_async, d_over, (uint32_t*)(ctx->d_pinned + 8000));
+    UQ_LAUNCH_CHECK();
     ctx->async_read = true;
     return 0;
 }

@@ -284,8 +284,9 @@ struct PackLists {
 };
 
 __global__ __launch_bounds__(256) void tile_origin_kernel(CensusView cv, const unsigned long long* __restrict__ d_async, const uint32_t* __restrict__ over, uint64_t first,
-                                                          uint64_t n, uint64_t R, uint64_t entries, TileRec* __restrict__ rec) {
+                                                          uint64_t n, uint64_t R, uint64_t entries, TileRec* __restrict__ rec, unsigned long long* __restrict__ bad) {
     const uint64_t tt = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (tt == 0) *bad = UQ_NONE;                    // the pack kernel's "no bad read yet" (this launch stands in front of it anyway: no clear of its own)
     if (tt >= entries) return;
     uint64_t nlines = 4 * (first + n);
     if (d_async) {                                  // the queued census: what it counted (pack_tile_kernel clips the same way)
@@ -748,6 +749,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
 #endif
         }
     }
+    // (*bad is UQ_NONE when this kernel starts: set by tile_origin_kernel in front of it with the census's lists, else by pack_impl's clear)
     if (badr != 0xFFFFFFFFu) atomicMin(bad, (unsigned long long)badr);
     if (bad_tile != UQ_NONE) atomicMin(bad, (unsigned long long)bad_tile);
     if (STATS) {
@@ -875,6 +877,8 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
     UQ_REQUIRE(ctx && d_buf && (d_line_start || use_lists) && hp && d_dna && d_qual && d_bad, "uq_pack: null argument");
     UQ_REQUIRE(!use_lists || (ctx->async_buf == d_buf && ctx->async_nbytes > 0), "uq_pack_stats_async: no line index given and no census of this buffer queued in front");
     if (h_fused) *h_fused = 0;
+    ctx->pk_stats = ctx->pk_q = nullptr;                         // (an epilogue that an earlier queued pack left pending is not this one's)
+    if (d_stats && ctx->stats_sent == (const void*)d_stats) ctx->stats_sent = nullptr;
     UQ_REQUIRE(hp->bits_per_base >= 1 && hp->bits_per_base <= 8 && hp->bits_per_quality >= 1 && hp->bits_per_quality <= 8,
                "uq_pack: bits per symbol must be 1..8");
     const uint32_t bd = hp->bits_per_base, bq = hp->bits_per_quality;
@@ -882,7 +886,13 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
     const uint32_t Lv = hp->dna_max + (hp->variable ? 1 : 0);
     UQ_REQUIRE(Cd == (bd * Lv + 7) / 8 && Cq == (bq * Lv + 7) / 8,
                "uq_pack: row bytes (%u, %u) do not match ceil(bits * (dna_max + variable) / 8)", Cd, Cq);
-    UQ_CHECK_HIP(hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
+    // *d_bad = UQ_NONE: with the census's lists tile_origin_kernel, queued in front of the pack kernel, sets it (no clear of its own in the
+    // step's chain); on every other way out of this function -- no fused kernel, or an error -- BadGuard's destructor queues the clear
+    struct BadGuard {
+        uint64_t* p; hipStream_t s; bool armed;
+        ~BadGuard() { if (armed) (void)hipMemsetAsync(p, 0xFF, 8, s); }
+    } bad_guard{d_bad, ctx->stream, use_lists && nreads != 0};
+    if (!bad_guard.armed) UQ_CHECK_HIP(hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
     if (nreads == 0) return 0;
 
     PackLut lut;
@@ -1004,8 +1014,10 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
             g.n_qchar = 0x01010101u * (uint32_t)(qmin + hp->n_qual[nchar]);       // (a code beyond the alphabet -- Q9 -- has no fused kernel: below)
         }
     }
-    if (d_stats && ntrick_bases == 1 && hp->n_qual[nchar] >= nq) return 0;    // the N-trick code is no quality of the alphabet (Q9): exact kernels only
-    if (d_stats && (!fast || (bd != 2 && bd != 3) || bq > 6)) return 0;  // the fused kernels exist for the lookup-free paths (2- / 3-bit bases, <= 64 contiguous qualities) only
+    if (d_stats && ((ntrick_bases == 1 && hp->n_qual[nchar] >= nq) ||         // the N-trick code is no quality of the alphabet (Q9): exact kernels only
+                    !fast || (bd != 2 && bd != 3) || bq > 6)) {               // the fused kernels exist for the lookup-free paths (2- / 3-bit bases, <= 64 contiguous qualities) only
+        return 0;
+    }
     const bool var_deal = d_stats && use_lists && hp->variable;
     const size_t lds_static = d_stats ? pks_words((int)bd, ntrick || d_q != nullptr) * 4 : 4;        // the kernels' count table
     const size_t lds = 16 + (size_t)g.stage_bytes + g.out_bytes + (4 * R + 4) * 4 + 3 * 512 + (d_stats ? sizeof(QnLds) : 0);
@@ -1049,8 +1061,9 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
         UQ_TRY(uq_scratch(ctx, entries * sizeof(TileRec) + 64, &scr));
         TileRec* rec = (TileRec*)scr;
         pl.over = (const uint32_t*)(ctx->idx_bitmap + pl.cv.nb * CV_LIST_CAP);        // index.hip: the 16 spare bytes behind the slots
-        tile_origin_kernel<<<(uint32_t)((entries + 255) / 256), 256, 0, ctx->stream>>>(pl.cv, d_async, pl.over, first_read, nreads, R, entries, rec);
+        tile_origin_kernel<<<(uint32_t)((entries + 255) / 256), 256, 0, ctx->stream>>>(pl.cv, d_async, pl.over, first_read, nreads, R, entries, rec, (unsigned long long*)d_bad);
         UQ_LAUNCH_CHECK();
+        bad_guard.armed = false;                     // (queued: *d_bad is set from here on)
         trec = rec;
     }
     k<<<(uint32_t)blocks, PK_THREADS, lds, ctx->stream>>>(d_buf, d_line_start, first_read, nreads, lut, g, d_dna, d_qual,
@@ -1098,5 +1111,9 @@ extern "C" int uq_pack_stats_qname_async(uq_ctx* ctx, const uint8_t* d_buf, cons
     UQ_REQUIRE(d_stats && h_fused && d_q && d_vals && vals_pitch >= capacity_reads, "uq_pack_stats_qname_async: null argument or columns shorter than the capacity");
     UQ_REQUIRE(ctx && ctx->async_buf == d_buf, "uq_pack_stats_qname_async: not the buffer of the last uq_count_lines_end_async");
     UQ_TRY(pack_impl(ctx, d_buf, d_line_start, 0, capacity_reads, h_guess, d_dna, d_qual, d_bad, d_stats, h_fused, ctx->d_async, d_q, d_vals, vals_pitch));
+    // the kernel is queued: uq_qname_fused_finish of this structure comes next and sends the census's words, the structure and these
+    // statistics (compacted in its epilogue launch) in one read-back; without it uq_count_lines_wait, uq_qname_fused_fetch and
+    // uq_stats_fetch_compact each send their own
+    if (*h_fused) { ctx->pk_stats = d_stats; ctx->pk_q = d_q; return 0; }
     return uq_async_read_back(ctx);
 }

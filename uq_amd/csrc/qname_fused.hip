@@ -9,11 +9,12 @@
 //   qname_guess_kernel    one lane: uq.py:428-444 on those numbers -> prefix / suffix lengths, ordered separators -> uq_qname_fused;
 // the pack kernel then verifies the guess on EVERY read while it tokenises (so nothing is assumed: see include/uqhip.h for why a
 // clean pass proves the layout is the reference's), and
-//   qf_first_seen_kernel / qf_count_kernel   count, per column of uint32 values, the distinct values among reads [0, T] at the
+//   qf_first_seen_kernel / qf_epilogue_kernel   count, per column of uint32 values, the distinct values among reads [0, T] at the
 //                         checkpoints of uq.py:586-602 (first occurrence per value by atomic minima; no sort).
 // Nothing here waits for the host: the read count is taken from the queued census (ctx->d_async) or from the structure itself.
 #include "common.h"
 #include "lines.h"
+#include "stats_compact.h"
 
 namespace {
 constexpr int QF_THREADS = 256;
@@ -210,7 +211,9 @@ __device__ bool regex_special(uint8_t c) {
 }
 
 // uq.py:428-444 on the sample's reductions -> the guess.  One wave.
-__global__ void qname_guess_kernel(const DevLine1* __restrict__ g_l1, const uq_qname_layout_result* __restrict__ g_lay, const uint32_t* __restrict__ step,
+// (g_lay is put back to the reductions' initial values once it has been copied: the structure is the context's own, and the next guess's
+// sample finds it as layout_init_kernel left it -- no initialising launch between the census and the sample)
+__global__ void qname_guess_kernel(const DevLine1* __restrict__ g_l1, uq_qname_layout_result* __restrict__ g_lay, const uint32_t* __restrict__ step,
                                    uq_qname_fused* __restrict__ q) {
     // the inputs are copied to LDS first: lane 0's loops below are serial, and a dependent global load costs ten LDS reads
     __shared__ DevLine1 s_l1;
@@ -218,6 +221,11 @@ __global__ void qname_guess_kernel(const DevLine1* __restrict__ g_l1, const uq_q
     for (uint32_t i = threadIdx.x; i < sizeof(DevLine1) / 4; i += 64) ((uint32_t*)&s_l1)[i] = ((const uint32_t*)g_l1)[i];
     for (uint32_t i = threadIdx.x; i < sizeof(uq_qname_layout_result) / 4; i += 64) ((uint32_t*)&s_lay)[i] = ((const uint32_t*)g_lay)[i];
     __syncthreads();
+    {   // what layout_init_kernel writes (one wave: lane t takes character t)
+        const uint32_t t0 = threadIdx.x;
+        if (t0 < QF_MAXCH) { g_lay->entry[t0] = UQ_NONE; g_lay->lastviol[t0] = 0; g_lay->ch[t0] = 0; }
+        if (t0 == 0) { g_lay->min_lcp = 0xFFFFFFFFu; g_lay->min_lcs = 0xFFFFFFFFu; g_lay->flags = 0; g_lay->nch = 0; }
+    }
     const DevLine1* l1 = &s_l1;
     const uq_qname_layout_result* lay = &s_lay;
     const uint32_t t = threadIdx.x;                           // one wave
@@ -285,15 +293,16 @@ __device__ __forceinline__ Checkpoints checkpoints(uint64_t n) {
 // first[col][v - vmin] = lowest read holding value v, for columns whose range is at most QF_SMALL: over all reads, through a private
 // LDS table per workgroup (a column of four lanes would otherwise be ten million atomics on four addresses).
 __global__ __launch_bounds__(QF_THREADS) void qf_first_seen_kernel(uq_qname_fused* __restrict__ q, const uint32_t* __restrict__ vals, uint64_t pitch,
-                                                                    uint32_t* __restrict__ first) {
+                                                                    uint32_t* __restrict__ first, uint32_t* __restrict__ compact_n) {
     __shared__ uint32_t s_first[QF_SMALL];
     const uint32_t col = blockIdx.y;
+    if (compact_n && blockIdx.x == 0 && col == 0 && threadIdx.x == 0) *compact_n = 0;      // the epilogue launch behind this one counts into it
     if (!q->ok || q->flags || col > q->nsep) return;
     const uint64_t n = q->nreads;
     const uint32_t vmin = q->vmin[col], vmax = q->vmax[col];
     if (n == 0 || vmin > vmax) return;
     const uint64_t range = (uint64_t)vmax - vmin + 1;
-    if (range > QF_SMALL) return;                                       // qf_wide_kernel's
+    if (range > QF_SMALL) return;                                       // qf_wide_part's
     const uint32_t* v = vals + col * pitch;
     uint32_t* f = first + (size_t)col * QF_SMALL;
     for (uint32_t i = threadIdx.x; i < (uint32_t)range; i += QF_THREADS) s_first[i] = 0xFFFFFFFFu;
@@ -330,10 +339,9 @@ __global__ __launch_bounds__(QF_THREADS) void qf_first_seen_kernel(uq_qname_fuse
 // the host sorts the column.  (A first-occurrence table over the first two million reads, as uq_int_prefix_distinct keeps it, is
 // two million contended global atomics: 0.1 ms for a decision the first 10 001 reads already give.)
 constexpr uint32_t QF_WIDE_CP = 3;
-__global__ __launch_bounds__(QF_THREADS) void qf_wide_kernel(uq_qname_fused* __restrict__ q, const uint32_t* __restrict__ vals, uint64_t pitch) {
+__device__ __forceinline__ void qf_wide_part(uq_qname_fused* __restrict__ q, const uint32_t* __restrict__ vals, uint64_t pitch, const uint32_t col) {
     extern __shared__ uint32_t bits[];                                  // QF_FT / 32 words
     __shared__ uint32_t s_count;
-    const uint32_t col = blockIdx.x;
     if (!q->ok || q->flags || col > q->nsep) return;
     const uint64_t n = q->nreads;
     const uint32_t vmin = q->vmin[col], vmax = q->vmax[col];
@@ -378,13 +386,15 @@ __global__ __launch_bounds__(QF_THREADS) void qf_wide_kernel(uq_qname_fused* __r
     if (!fired && k < cp.nth && threadIdx.x == 0) q->undetermined[col] = 1;      // checkpoints left that were not evaluated
 }
 
-__global__ __launch_bounds__(QF_THREADS) void qf_count_kernel(uq_qname_fused* __restrict__ q, const uint32_t* __restrict__ first) {
+// (restores every entry of `first` it has read to 0xFFFFFFFF: the tables are the context's own and stay all-ones between two calls of
+// uq_qname_fused_finish -- qf_first_seen_kernel writes under exactly the conditions this kernel reads under -- so no fill is queued per call)
+constexpr uint32_t QF_COUNT_WG = 4;                                     // workgroups that share a column's table
+__device__ __forceinline__ void qf_count_part(uq_qname_fused* __restrict__ q, uint32_t* __restrict__ first, const uint32_t part, const uint32_t col) {
     __shared__ uint32_t s_cnt[UQ_QF_MAXT];
-    const uint32_t col = blockIdx.y;
     if (!q->ok || q->flags || col > q->nsep) return;
     const uint64_t n = q->nreads;
     const Checkpoints cp = checkpoints(n);
-    if (col == 0 && blockIdx.x == 0 && threadIdx.x == 0) { q->nth = cp.nth; for (uint32_t k = 0; k < cp.nth; ++k) q->thresholds[k] = cp.t[k]; }
+    if (col == 0 && part == 0 && threadIdx.x == 0) { q->nth = cp.nth; for (uint32_t k = 0; k < cp.nth; ++k) q->thresholds[k] = cp.t[k]; }
     const uint32_t vmin = q->vmin[col], vmax = q->vmax[col];
     if (n == 0 || vmin > vmax) return;
     const uint64_t range = (uint64_t)vmax - vmin + 1;
@@ -392,15 +402,39 @@ __global__ __launch_bounds__(QF_THREADS) void qf_count_kernel(uq_qname_fused* __
     const uint32_t nth = cp.nth;
     if (threadIdx.x < UQ_QF_MAXT) s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    const uint32_t* f = first + (size_t)col * QF_SMALL;
-    for (uint64_t j = (uint64_t)blockIdx.x * QF_THREADS + threadIdx.x; j < range; j += (uint64_t)gridDim.x * QF_THREADS) {
+    uint32_t* f = first + (size_t)col * QF_SMALL;
+    for (uint64_t j = (uint64_t)part * QF_THREADS + threadIdx.x; j < range; j += (uint64_t)QF_COUNT_WG * QF_THREADS) {
         const uint32_t at = f[j];
         if (at == 0xFFFFFFFFu) continue;
+        f[j] = 0xFFFFFFFFu;
         for (uint32_t k = 0; k < nth; ++k)
             if (at <= cp.t[k]) atomicAdd(&s_cnt[k], 1u);
     }
     __syncthreads();
     if (threadIdx.x < nth && s_cnt[threadIdx.x]) atomicAdd((unsigned long long*)&q->counts[col][threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
+// ONE launch behind qf_first_seen_kernel whose workgroups take roles: the wide-range columns (a workgroup each; first in the grid, they run
+// longest), the small-range columns' counts (QF_COUNT_WG workgroups each), and -- st != nullptr -- the statistics of the pack kernel as
+// the list of their non-zero counters (EP_COMPACT_WG workgroups).  The three read different inputs and write different outputs.
+constexpr uint32_t EP_COMPACT_WG = 64, EP_WG = UQ_QF_MAXC + UQ_QF_MAXC * QF_COUNT_WG + EP_COMPACT_WG;
+__global__ __launch_bounds__(QF_THREADS) void qf_epilogue_kernel(uq_qname_fused* __restrict__ q, uint32_t* __restrict__ first, const uint32_t* __restrict__ vals,
+                                                                  uint64_t pitch, const uq_stats* __restrict__ st, uq_stats_compact* __restrict__ compact) {
+    const uint32_t b = blockIdx.x;                                      // (the role is the workgroup's: every branch below is uniform)
+    if (b < UQ_QF_MAXC) { qf_wide_part(q, vals, pitch, b); return; }
+    if (b < UQ_QF_MAXC + UQ_QF_MAXC * QF_COUNT_WG) { const uint32_t k = b - UQ_QF_MAXC; qf_count_part(q, first, k % QF_COUNT_WG, k / QF_COUNT_WG); return; }
+    if (!st) return;
+    const uint32_t w = b - UQ_QF_MAXC - UQ_QF_MAXC * QF_COUNT_WG;
+    for (uint32_t i = w * (65536 / EP_COMPACT_WG) + threadIdx.x; i < (w + 1) * (65536 / EP_COMPACT_WG); i += QF_THREADS) stats_compact_one(st, compact, i);
+}
+
+// the census's words, the structure and the compacted statistics -> the pinned staging, in ONE launch (uq_read_back's reasons: no copy command)
+struct GatherSeg { const uint32_t* src; uint32_t* dst; uint32_t nwords; uint32_t pad; };
+struct Gather { GatherSeg s[4]; };
+__global__ __launch_bounds__(QF_THREADS) void gather_read_back_kernel(Gather g) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (uint32_t i = blockIdx.x * QF_THREADS + threadIdx.x; i < g.s[k].nwords; i += gridDim.x * QF_THREADS) g.s[k].dst[i] = g.s[k].src[i];
 }
 
 template <typename T>
@@ -424,20 +458,27 @@ int guess_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, 
         over = (const uint32_t*)(ctx->idx_bitmap + cv.nb * CV_LIST_CAP);
     }
     ScratchPlan sp;
-    const size_t o_lay = sp.add(sizeof(uq_qname_layout_result)), o_l1 = sp.add(sizeof(DevLine1)), o_step = sp.add(16);
+    const size_t o_l1 = sp.add(sizeof(DevLine1)), o_step = sp.add(16);
     void* scr;
     UQ_TRY(uq_scratch(ctx, sp.off, &scr));
     uint8_t* base = (uint8_t*)scr;
-    uq_qname_layout_result* d_lay = (uq_qname_layout_result*)(base + o_lay);
-    // initial values of the reductions: min_lcp = min_lcs = 0xFFFFFFFF (clamped to line 1's length by the guess kernel), entry = none
-    layout_init_kernel<<<1, 256, 0, ctx->stream>>>(d_lay);             // (one launch instead of three fills)
-    UQ_LAUNCH_CHECK();
+    // initial values of the reductions: min_lcp = min_lcs = 0xFFFFFFFF (clamped to line 1's length by the guess kernel), entry = none.  The
+    // structure is the context's own and initialised once: qname_guess_kernel puts it back as it found it -- unless a call got no further
+    // than the sample (an error return below; a launch that faults on the device leaves a context that is not usable anyway)
+    if (!ctx->qf_lay) { UQ_CHECK_HIP(hipMalloc(&ctx->qf_lay, sizeof(uq_qname_layout_result))); ctx->qf_lay_dirty = true; }
+    uq_qname_layout_result* d_lay = (uq_qname_layout_result*)ctx->qf_lay;
+    if (ctx->qf_lay_dirty) {
+        layout_init_kernel<<<1, 256, 0, ctx->stream>>>(d_lay);
+        UQ_LAUNCH_CHECK();
+    }
+    ctx->qf_lay_dirty = true;
     const uint32_t grid = QF_SAMPLES / QF_SPW;
     qname_sample_kernel<<<grid, 64, 0, ctx->stream>>>(d_buf, d_line_start, nreads, d_async, d_lay, (DevLine1*)(base + o_l1), (uint32_t*)(base + o_step), cv,
                                                       use_lists ? ctx->async_nbytes : 0, over);
     UQ_LAUNCH_CHECK();
     qname_guess_kernel<<<1, 64, 0, ctx->stream>>>((const DevLine1*)(base + o_l1), d_lay, (const uint32_t*)(base + o_step), d_q);
     UQ_LAUNCH_CHECK();
+    ctx->qf_lay_dirty = false;
     return 0;
 }
 }  // namespace
@@ -453,21 +494,40 @@ extern "C" int uq_qname_guess_async(uq_ctx* ctx, const uint8_t* d_buf, const uin
 
 extern "C" int uq_qname_fused_finish(uq_ctx* ctx, uq_qname_fused* d_q, const uint32_t* d_vals, uint64_t vals_pitch) {
     UQ_REQUIRE(ctx && d_q && d_vals, "uq_qname_fused_finish: null argument");
-    void* scr;
+    // the statistics of the queued pack kernel this structure rode in (uq_pack_stats_qname_async noted them), else none
+    const uq_stats* st = ctx->pk_q == (const void*)d_q ? (const uq_stats*)ctx->pk_stats : nullptr;
+    ctx->pk_stats = ctx->pk_q = nullptr;
     const size_t bytes = (size_t)UQ_QF_MAXC * QF_SMALL * sizeof(uint32_t);
-    UQ_TRY(uq_scratch(ctx, bytes, &scr));
-    UQ_CHECK_HIP(hipMemsetAsync(scr, 0xFF, bytes, ctx->stream));
-    qf_first_seen_kernel<<<dim3(UQ_NUM_CU * 4, UQ_QF_MAXC), QF_THREADS, 0, ctx->stream>>>(d_q, d_vals, vals_pitch, (uint32_t*)scr);
+    if (!ctx->qf_first) { UQ_CHECK_HIP(hipMalloc((void**)&ctx->qf_first, bytes)); ctx->qf_dirty = true; }
+    if (!ctx->d_compact) UQ_CHECK_HIP(hipMalloc((void**)&ctx->d_compact, sizeof(uq_stats_compact)));
+    // filled once: qf_count_part leaves the tables as it found them -- unless a call got no further than qf_first_seen_kernel (an error below).
+    // (A launch that was accepted and then faulted on the device is not seen here: a context whose stream has faulted is not usable anyway.)
+    if (ctx->qf_dirty) UQ_CHECK_HIP(hipMemsetAsync(ctx->qf_first, 0xFF, bytes, ctx->stream));
+    ctx->qf_dirty = true;
+    if (!ctx->qf_attr_set) { UQ_CHECK_HIP(hipFuncSetAttribute((const void*)qf_epilogue_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(QF_FT / 8))); ctx->qf_attr_set = true; }
+    qf_first_seen_kernel<<<dim3(UQ_NUM_CU * 4, UQ_QF_MAXC), QF_THREADS, 0, ctx->stream>>>(d_q, d_vals, vals_pitch, ctx->qf_first, st ? &ctx->d_compact->n : nullptr);
     UQ_LAUNCH_CHECK();
-    qf_count_kernel<<<dim3(4, UQ_QF_MAXC), QF_THREADS, 0, ctx->stream>>>(d_q, (const uint32_t*)scr);
+    qf_epilogue_kernel<<<EP_WG, QF_THREADS, QF_FT / 8, ctx->stream>>>(d_q, ctx->qf_first, d_vals, vals_pitch, st, ctx->d_compact);
     UQ_LAUNCH_CHECK();
-    if (!ctx->qf_attr_set) { UQ_CHECK_HIP(hipFuncSetAttribute((const void*)qf_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(QF_FT / 8))); ctx->qf_attr_set = true; }
-    qf_wide_kernel<<<UQ_QF_MAXC, QF_THREADS, QF_FT / 8, ctx->stream>>>(d_q, d_vals, vals_pitch);
+    ctx->qf_dirty = false;
+    // everything the host waits for is sent on its way right away, in one launch, to regions of the pinned staging that nothing else uses:
+    // uq_qname_fused_fetch, uq_count_lines_wait and uq_stats_fetch_compact then only wait -- a read-back queued by them would start a host
+    // round trip later.  What is not pending here (no census queued, no statistics noted) those calls send themselves.
+    Gather g;
+    memset(&g, 0, sizeof(g));
+    g.s[0] = GatherSeg{(const uint32_t*)d_q, (uint32_t*)(ctx->d_pinned + QF_PINNED_AT), (uint32_t)(sizeof(uq_qname_fused) / 4), 0};
+    const uint32_t *d_async, *d_over;
+    const bool census = uq_async_sources(ctx, &d_async, &d_over);
+    if (census) {
+        g.s[1] = GatherSeg{d_async, (uint32_t*)(ctx->d_pinned + 8000), 4, 0};
+        g.s[2] = GatherSeg{d_over, (uint32_t*)(ctx->d_pinned + 8002), 1, 0};
+    }
+    if (st) g.s[3] = GatherSeg{(const uint32_t*)ctx->d_compact, (uint32_t*)(ctx->d_pinned + 8192), (uint32_t)(sizeof(uq_stats_compact) / 4), 0};
+    gather_read_back_kernel<<<st ? 8 : 1, QF_THREADS, 0, ctx->stream>>>(g);
     UQ_LAUNCH_CHECK();
-    // the structure is sent on its way to the host right away (a region of the pinned staging that nothing else uses):
-    // uq_qname_fused_fetch then only waits -- a read-back queued by the fetch itself would start a host round trip later
-    UQ_TRY(uq_read_back(ctx, ctx->h_pinned + QF_PINNED_AT, d_q, sizeof(uq_qname_fused)));
     ctx->qf_sent = d_q;
+    if (census) ctx->async_read = true;
+    if (st) ctx->stats_sent = st;
     return 0;
 }
 

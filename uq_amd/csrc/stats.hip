@@ -17,6 +17,7 @@
 // straight from HBM.
 // Algorithmic HBM bytes: the record bytes once + 32 B of line offsets per record.
 #include "common.h"
+#include "stats_compact.h"
 #include "swar.h"
 
 namespace {
@@ -322,17 +323,7 @@ __global__ void stats_import_kernel(const long long* __restrict__ buf, uint32_t 
 constexpr uint32_t SC_CAP = UQ_STATS_COMPACT_CAP;
 typedef uq_stats_compact StatsCompact;
 __global__ void stats_compact_kernel(const uq_stats* __restrict__ st, StatsCompact* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        out->len_min = st->len_min; out->len_max = st->len_max; out->max_record_bytes = st->max_record_bytes; out->reserved = st->reserved;
-        out->bad_plus = st->bad_plus; out->bad_len = st->bad_len;
-    }
-    if (i >= 65536) return;
-    const uint64_t c = st->counts[i];
-    if (c) {
-        const uint32_t k = atomicAdd(&out->n, 1u);
-        if (k < SC_CAP) { out->key[k] = i; out->count[k] = c; }
-    }
+    stats_compact_one(st, out, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ void stats_init_kernel(uq_stats* st) {
@@ -374,6 +365,12 @@ __global__ __launch_bounds__(256) void first_occurrence_kernel(const uint8_t* __
 // the non-zero counters as a list (n entries, any order) + the scalars, in the context's pinned staging; n > SC_CAP: list cut short
 static int stats_fetch_compact(uq_ctx* ctx, const uq_stats* d_stats, const StatsCompact** out) {
     static_assert(sizeof(StatsCompact) <= 63000 && sizeof(StatsCompact) % 4 == 0, "the compact form must fit the context's pinned staging buffer");
+    if (ctx->stats_sent == (const void*)d_stats) {          // uq_qname_fused_finish's epilogue compacted these statistics and its read-back sent them
+        ctx->stats_sent = nullptr;
+        UQ_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        *out = (const StatsCompact*)(ctx->h_pinned + 8192);
+        return 0;
+    }
     void* scr;
     UQ_TRY(uq_scratch(ctx, sizeof(StatsCompact), &scr));
     UQ_CHECK_HIP(hipMemsetAsync(scr, 0, 8, ctx->stream));
@@ -414,6 +411,7 @@ extern "C" int uq_stats_fetch_compact(uq_ctx* ctx, const uq_stats* d_stats, uq_s
 
 extern "C" int uq_stats_init(uq_ctx* ctx, uq_stats* d_stats) {
     UQ_REQUIRE(ctx && d_stats, "uq_stats_init: null argument");
+    if (ctx->stats_sent == (const void*)d_stats) ctx->stats_sent = nullptr;      // (what was sent is no longer what the structure holds)
     stats_init_kernel<<<256, 256, 0, ctx->stream>>>(d_stats);
     UQ_LAUNCH_CHECK();
     return 0;
@@ -429,6 +427,7 @@ extern "C" int uq_stats_export(uq_ctx* ctx, const uq_stats* d_stats, uint32_t ra
 
 extern "C" int uq_stats_import(uq_ctx* ctx, const int64_t* d_words, uint32_t world, uq_stats* d_stats) {
     UQ_REQUIRE(ctx && d_stats && d_words && world >= 1, "uq_stats_import: bad argument");
+    if (ctx->stats_sent == (const void*)d_stats) ctx->stats_sent = nullptr;
     stats_import_kernel<<<256, 256, 0, ctx->stream>>>((const long long*)d_words, world, d_stats);
     UQ_LAUNCH_CHECK();
     return 0;
@@ -437,6 +436,7 @@ extern "C" int uq_stats_import(uq_ctx* ctx, const int64_t* d_words, uint32_t wor
 extern "C" int uq_stats_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start,
                                    uint64_t first_read, uint64_t nreads, uq_stats* d_stats) {
     UQ_REQUIRE(ctx && d_buf && d_line_start && d_stats, "uq_stats_accumulate: null argument");
+    if (ctx->stats_sent == (const void*)d_stats) ctx->stats_sent = nullptr;
     if (nreads == 0) return 0;
     // No host round trip: tile size and table windows are derived on the device (kernel prologue).  The grid
     // only needs an upper bound of the tile count (tiles hold >= 1 record); surplus workgroups exit at once.

@@ -79,15 +79,22 @@ class HostStats:
     counters as a list (nz_keys = base * 256 + quality, nz_counts) and builds the dense table only when somebody asks for it."""
 
     def __init__(self, s):
-        """`s`: a ctypes `Stats`, a numpy record of STATS_DTYPE (same layout) or one of STATS_COMPACT_DTYPE."""
+        """`s`: a ctypes `Stats`, a numpy record of STATS_DTYPE (same layout) or one of STATS_COMPACT_DTYPE -- or the one-element array of
+        STATS_COMPACT_DTYPE that holds it, which is then kept as it is (no copy)."""
+        own = None
+        if isinstance(s, np.ndarray) and s.dtype == STATS_COMPACT_DTYPE and s.shape == (1,):
+            own, s = s, s[0]
         if isinstance(s, Stats):
             s = np.frombuffer(s, dtype=STATS_DTYPE, count=1)[0]
+        self.compact = None                           # the uq_stats_compact itself (a one-element array): what uq_decide_from_stats reads
+        self._nz = None
         if 'key' in s.dtype.names:
-            n = int(s['n'])
-            self.nz_keys = s['key'][:n].astype(np.int64); self.nz_counts = s['count'][:n].astype(np.int64)
+            self.compact = own
+            if self.compact is None:
+                self.compact = np.empty(1, dtype=STATS_COMPACT_DTYPE)
+                self.compact[0] = s
             self._counts = None
         else:
-            self.nz_keys = self.nz_counts = None
             self._counts = s['counts'].reshape(256, 256).copy()
         bad_plus, bad_len = int(s['bad_plus']), int(s['bad_len'])
         self.bad_plus = None if bad_plus == UQ_NONE else bad_plus
@@ -95,6 +102,21 @@ class HostStats:
         self.len_min, self.len_max = int(s['len_min']), int(s['len_max'])
         self.max_record_bytes = int(s['max_record_bytes'])
         self.incomplete = bool(s['reserved'])         # set by uq_pack_stats only: counts not usable
+
+    def _pairs(self):
+        if self._nz is None:
+            c = self.compact[0]
+            n = int(c['n'])
+            self._nz = (c['key'][:n].astype(np.int64), c['count'][:n].astype(np.int64))
+        return self._nz
+
+    @property
+    def nz_keys(self):
+        return None if self.compact is None else self._pairs()[0]
+
+    @property
+    def nz_counts(self):
+        return None if self.compact is None else self._pairs()[1]
 
     @property
     def counts(self):
@@ -130,7 +152,7 @@ def stats_fetch(ctx, d_stats):
     raw = np.empty(1, dtype=STATS_COMPACT_DTYPE)
     call('uq_stats_fetch_compact', ctx.h, _p(d_stats), C.c_void_p(raw.ctypes.data))
     if int(raw[0]['n']) <= STATS_COMPACT_CAP:
-        return HostStats(raw[0])
+        return HostStats(raw)
     raw = np.empty(1, dtype=STATS_DTYPE)              # more non-zero counters than the list holds: the whole table
     call('uq_stats_fetch', ctx.h, _p(d_stats), C.c_void_p(raw.ctypes.data))
     return HostStats(raw[0])
@@ -223,6 +245,19 @@ def fingerprint_json(fp):
 # ------------------------------------------------------------------ pack
 def make_pack_params(bases, qualities, N_qual, bits_per_base, bits_per_quality, variable,
                      dna_bytes_per_row, quality_bytes_per_row, dna_max, max_record_bytes, avg_record_bytes=0):
+    """uq_pack_params from the decisions (uq_make_pack_params: the tables are filled in the library)."""
+    p = PackParams()
+    k = len(N_qual)
+    call('uq_make_pack_params', bases.encode('latin-1'), len(bases), qualities.encode('latin-1'), len(qualities),
+         ''.join(N_qual).encode('latin-1'), (C.c_int32 * max(k, 1))(*[int(v) for v in N_qual.values()]), k,
+         int(bits_per_base), int(bits_per_quality), 1 if variable else 0, int(dna_bytes_per_row), int(quality_bytes_per_row), int(dna_max),
+         int(max_record_bytes), int(avg_record_bytes), C.byref(p))
+    return p
+
+
+def make_pack_params_py(bases, qualities, N_qual, bits_per_base, bits_per_quality, variable,
+                        dna_bytes_per_row, quality_bytes_per_row, dna_max, max_record_bytes, avg_record_bytes=0):
+    """The numpy twin of uq_make_pack_params (what make_pack_params ran before; the tests compare the two byte for byte)."""
     p = PackParams()
     dna_code = np.full(256, -1, dtype=np.int16); qual_code = np.full(256, -1, dtype=np.int16); n_qual = np.full(256, -1, dtype=np.int32)
     dna_code[np.frombuffer(bases.encode('latin-1'), dtype=np.uint8)] = np.arange(len(bases), dtype=np.int16)
@@ -408,7 +443,14 @@ def head_guess_indexed(ctx, buf, line_start, nreads, notricks=False, pad=False):
 
 
 def same_pack_params(a, b):
-    """Do two uq_pack_params describe the same encoding (everything but the tile-sizing hint)?"""
+    """Do two uq_pack_params describe the same encoding (everything but the tile-sizing hints)?  (uq_same_pack_params)"""
+    same = C.c_int(0)
+    call('uq_same_pack_params', C.byref(a), C.byref(b), C.byref(same))
+    return bool(same.value)
+
+
+def same_pack_params_py(a, b):
+    """The Python twin of uq_same_pack_params."""
     if (a.bits_per_base, a.bits_per_quality, a.variable, a.dna_bytes_per_row, a.quality_bytes_per_row, a.dna_max) != \
        (b.bits_per_base, b.bits_per_quality, b.variable, b.dna_bytes_per_row, b.quality_bytes_per_row, b.dna_max):
         return False

@@ -235,23 +235,22 @@ def type_and_encode_device(ctx, d_buf, d_ls, nreads, prefix, suffix, separators,
     return columns, arrays
 
 
-def analyse_fused(ctx, fq, nreads):
-    """The QNAME analysis from what the pack kernel's QNAME phase left behind (ops.FusedQname after pack_stats(fq=...) and
-    qname_fused_finish): (prefix, suffix, separators, columns, device column tensors), or None when the fused pass cannot vouch for
-    it -- the guess declined, a read did not conform (any flag), a column needs the sorted map or the sort-based distinct counts --
-    and the caller runs analyse_device.  One host wait (the fetch); the column encoders are queued behind it."""
-    r = ops.qname_fused_fetch(ctx, fq)
-    n = int(nreads)
+DECLINE, NEEDS_SORT = 'decline', 'needs sort'
+_DT_OF_ITEMSIZE = {1: 'uint8', 2: 'uint16', 4: 'uint32', 8: 'uint64'}
+
+
+def fused_columns_py(r, n, sorted_counts=None):
+    """The column typing of uq.py:586-678 from a fetched uq_qname_fused `r` for n reads: the list of column descriptions, DECLINE (the
+    fused pass cannot vouch for the file: no guess, a flag, another read count or other checkpoints, a column that stays a mapping of
+    strings) or NEEDS_SORT (a column's distinct counts have to come from a sort of its values: sorted_counts(c) -> (counts at every
+    checkpoint, distinct values), when given, supplies them).  The Python twin of uq_qname_fused_columns (csrc/decide.hip), which
+    analyse_fused runs; the tests compare the two."""
     if not r.ok or r.flags or n == 0 or int(r.nreads) != n:
-        return None
-    l1 = bytes(r.line1[:r.l1len]).decode('latin-1')
-    prefix = l1[:r.plen]
-    suffix = l1[r.l1len - r.slen:] if r.slen else ''
-    separators = bytes(r.seps[:r.nsep]).decode('latin-1')
+        return DECLINE
     thresholds = _thresholds(n)
     if list(r.thresholds[:r.nth]) != thresholds:
-        return None
-    columns, arrays = [], []
+        return DECLINE
+    columns = []
     for c in range(r.nsep + 1):
         vmin, vmax = int(r.vmin[c]), int(r.vmax[c])
         col = {'name': 'QNAME_%d' % (c + 1), 'format': 'mapping'}
@@ -269,9 +268,10 @@ def analyse_fused(ctx, fq, nreads):
             elif len(ths) == len(thresholds): nu = counts[-1]
             else: counts = None
         if counts is None:                                  # a stable sort of the 4-byte values (any order will do for counting)
-            perm, _, skey, _, nu = ops.unique_rows(ctx, fq.column(c, n).view(ctx.torch.uint8), n, 4, want_key=False, want_unique=False)
-            ths, counts = thresholds, ops.prefix_distinct(ctx, perm, skey, n, thresholds)
-            del perm, skey
+            if sorted_counts is None:
+                return NEEDS_SORT
+            ths = thresholds
+            counts, nu = sorted_counts(c)
         for T, cnt in zip(ths, counts):
             if cnt > T // 10:                               # check_format(): mapping -> integers
                 col['format'] = 'integers'
@@ -280,7 +280,7 @@ def analyse_fused(ctx, fq, nreads):
             lim, dt = _ladder(nu)
             col['dtype'] = dt
             if vmax - vmin > lim:
-                return None                                 # stays a mapping: the sorted map of its strings comes from the exact path
+                return DECLINE                              # stays a mapping: the sorted map of its strings comes from the exact path
             col['format'] = 'integers'; col['max'] = vmax; col['min'] = vmin
             col['offset'] = bool(vmax > lim)
         else:
@@ -289,6 +289,47 @@ def analyse_fused(ctx, fq, nreads):
             col['dtype'] = dt
             col['offset'] = bool(vmax > lim)
         columns.append(col)
+    return columns
+
+
+def fused_columns(r, n):
+    """uq_qname_fused_columns: the same answer as fused_columns_py(r, n) from the library."""
+    import ctypes as C
+    from ._lib import QnameColumns, call
+    out = QnameColumns()
+    call('uq_qname_fused_columns', C.byref(r), int(n), C.byref(out))
+    if out.status:
+        return DECLINE if out.status == 1 else NEEDS_SORT
+    columns = []
+    for c in range(out.ncols):
+        dt = _DT_OF_ITEMSIZE[out.itemsize[c]]
+        if out.from_mapping[c]:
+            columns.append({'name': 'QNAME_%d' % (c + 1), 'format': 'integers', 'dtype': dt, 'max': out.vmax[c], 'min': out.vmin[c], 'offset': bool(out.offset[c])})
+        else:
+            columns.append({'name': 'QNAME_%d' % (c + 1), 'format': 'integers', 'min': out.vmin[c], 'max': out.vmax[c], 'dtype': dt, 'offset': bool(out.offset[c])})
+    return columns
+
+
+def analyse_fused(ctx, fq, nreads):
+    """The QNAME analysis from what the pack kernel's QNAME phase left behind (ops.FusedQname after pack_stats(fq=...) and
+    qname_fused_finish): (prefix, suffix, separators, columns, device column tensors), or None when the fused pass cannot vouch for
+    it -- the guess declined, a read did not conform (any flag), a column needs the sorted map -- and the caller runs analyse_device.
+    One host wait (the fetch); the columns are typed in the library (uq_qname_fused_columns) and their encoders queued behind it.  A
+    column whose distinct counts need a sort of its values goes through the Python rules, with the sort."""
+    r = ops.qname_fused_fetch(ctx, fq)
+    n = int(nreads)
+    columns = fused_columns(r, n)
+    if columns == NEEDS_SORT:
+        def sorted_counts(c):
+            perm, _, skey, _, nu = ops.unique_rows(ctx, fq.column(c, n).view(ctx.torch.uint8), n, 4, want_key=False, want_unique=False)
+            return ops.prefix_distinct(ctx, perm, skey, n, _thresholds(n)), nu
+        columns = fused_columns_py(r, n, sorted_counts)
+    if columns == DECLINE:
+        return None
+    l1 = bytes(r.line1[:r.l1len]).decode('latin-1')
+    prefix = l1[:r.plen]
+    suffix = l1[r.l1len - r.slen:] if r.slen else ''
+    separators = bytes(r.seps[:r.nsep]).decode('latin-1')
     arrays = ops.encode_u32_columns(ctx, fq, n, [c['min'] if c['offset'] else 0 for c in columns], [np.dtype(c['dtype']).itemsize for c in columns])
     return prefix, suffix, separators, columns, arrays
 
@@ -355,7 +396,7 @@ def analyse_fused_sharded(ctx, fq, nreads, shard, usable=True):
         for c in small:
             row = tab[c][:ranges[c]]
             counts_small[c] = [int((row <= T).sum()) for T in thresholds]
-    head = [T for T in thresholds if T < INT_PREFIX][:3]                   # the checkpoints the wide-range kernel looks at (qf_wide_kernel)
+    head = [T for T in thresholds if T < INT_PREFIX][:3]                   # the checkpoints the wide-range kernel looks at (qf_wide_part)
     columns = []
     for c in range(ncols):
         vmin, vmax = gvmin[c], gvmax[c]
