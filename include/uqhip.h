@@ -140,7 +140,23 @@ int uq_fingerprint_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t*
 int uq_fingerprint_host(const uint8_t* h_buf, const uint64_t* h_line_start,
                         uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uq_fingerprint* h_fp);
 
-/* ---- a3 / a4: the per-read packers.  Replaces `encoder_fixed` (uq.py:108-182) and
+/* ---- quality binning (`--bin-qual`; an extension: the reference stores the qualities it is given).  LOSSY by request:
+ * a byte table applied to the quality lines of a FASTQ text before anything else looks at it.
+ * uq_requantise_qualities applies lut[] to every byte of line 4 (the quality line, without its '\n') of the records
+ * [first_read, first_read + nreads) of d_buf, in place.  No other byte of d_buf is written.  d_line_start as uq_index_lines writes it.
+ * h_lut: 256 bytes on the host, no entry may be '\n' (refused with an error: line ends must stay where they are, so the index stays valid) -- except
+ * lut['\n'] itself, which no line ever looks up, so that the identity table passes.
+ * d_changed (may be NULL): device u64, 8-byte aligned; the number of bytes whose value changed is ADDED to it (calls and shards add).
+ * Queued on the context's stream; nothing is read back.  Any buffer alignment; lines shorter than 2^32 bytes; offsets are 64-bit everywhere.
+ * The kernel reads the quality lines and 16 B of line starts per record, and writes the quality lines; an item stores only bytes of its
+ * own line (whole 16-byte vectors and dwords inside a line, single bytes at its ends), so lines that share a vector do not race.
+ * uq_requantise_qualities_host: the same, sequentially, on host memory (needs no GPU; ADDS into *h_changed, which may be NULL). */
+int uq_requantise_qualities(uq_ctx* ctx, uint8_t* d_buf, const uint64_t* d_line_start,
+                            uint64_t first_read, uint64_t nreads, const uint8_t* h_lut, uint64_t* d_changed);
+int uq_requantise_qualities_host(uint8_t* h_buf, const uint64_t* h_line_start,
+                                 uint64_t first_read, uint64_t nreads, const uint8_t* h_lut, uint64_t* h_changed);
+
+/* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */
 typedef struct uq_pack_params {

@@ -139,6 +139,8 @@ SIGNATURES = {
     'uq_fingerprint_init': [_vp, _vp],
     'uq_fingerprint_accumulate': [_vp, _vp, _vp, _u64, _u64, _u64, _vp],
     'uq_fingerprint_host': [_vp, _vp, _u64, _u64, _u64, _P(Fingerprint)],
+    'uq_requantise_qualities': [_vp, _vp, _vp, _u64, _u64, _vp, _vp],
+    'uq_requantise_qualities_host': [_vp, _vp, _u64, _u64, _vp, _P(_u64)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

@@ -166,6 +166,12 @@ class ShardedSession(Session):
     def reads_in_file(self):
         return self.total_reads
 
+    def binned_changed_in_file(self):
+        """--bin-qual: every rank binned its own shard at the head of load_device; the file's count is the sum (collective)."""
+        if getattr(self, '_binned_total', None) is None:
+            self._binned_total = int(self.shard.reduce([int(self.binned_changed)], 'sum')[0])
+        return self._binned_total
+
     def analyse_qname(self):
         from . import qname, qname_device
         res = None

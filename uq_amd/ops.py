@@ -242,6 +242,40 @@ def fingerprint_json(fp):
     return json.dumps(d)
 
 
+# ------------------------------------------------------------------ quality binning (include/uqhip.h)
+def _lut_arg(lut):
+    a = np.ascontiguousarray(np.frombuffer(bytes(lut), dtype=np.uint8))
+    if a.size != 256: raise ValueError('a quality table has 256 entries, not %d' % a.size)
+    return a
+
+
+def changed_new(ctx):
+    """A zeroed device u64 (int64[1]) for uq_requantise_qualities to add its count of changed bytes to."""
+    t = ctx.torch
+    return t.zeros(1, dtype=t.int64, device=ctx.device)
+
+
+def requantise_qualities(ctx, buf, line_start, first_read, nreads, lut, d_changed=None):
+    """lut[] applied in place to the quality lines of the records [first_read, first_read + nreads) of buf (queued, nothing read back); the
+    number of bytes that changed is added to d_changed (changed_new) when given."""
+    a = _lut_arg(lut)
+    call('uq_requantise_qualities', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), C.c_void_p(a.ctypes.data), _p(d_changed))
+
+
+def requantise_qualities_host(data, lut, line_start=None, first_read=0, nreads=None):
+    """uq_requantise_qualities_host: the same on the CPU over host bytes (needs no GPU).  Returns (a new uint8 array, bytes changed)."""
+    out = np.array(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8, order='C')
+    ls = np.ascontiguousarray(host_line_starts(out) if line_start is None else line_start, dtype=np.uint64)
+    if nreads is None:
+        if (len(ls) - 1) % 4: raise ValueError('requantise: %d lines are not whole FASTQ records' % (len(ls) - 1))
+        nreads = (len(ls) - 1) // 4 - first_read
+    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('requantise: records beyond the index')
+    a, changed = _lut_arg(lut), C.c_uint64(0)
+    call('uq_requantise_qualities_host', C.c_void_p(out.ctypes.data if out.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
+         C.c_void_p(a.ctypes.data), C.byref(changed))
+    return out, changed.value
+
+
 # ------------------------------------------------------------------ pack
 def make_pack_params(bases, qualities, N_qual, bits_per_base, bits_per_quality, variable,
                      dna_bytes_per_row, quality_bytes_per_row, dna_max, max_record_bytes, avg_record_bytes=0):

@@ -87,6 +87,8 @@ def build_parser():
     p.add_argument('--fingerprint', action='store_true', default=False,
                    help='print the record fingerprint (uqfp1, DESIGN.md section 19: not cryptographic) of the input FASTQ as one JSON line and '
                         'write no container; with --decode: of the decoded text, and write no text (extension)')
+    from . import binqual
+    p.add_argument('--bin-qual', action='store', default=None, metavar='SPEC', help=binqual.HELP)
     return p
 
 
@@ -125,8 +127,22 @@ def validate_args(args):
         if getattr(args, 'bgzf', False): error('ERROR: --fingerprint writes no text, so there is nothing for --bgzf to compress')
         if getattr(args, 'gz', False) or args.peek or args.test or args.output:
             error('ERROR: --fingerprint only reads: it does not go with --gz, --peek, --test or -o')
+    if getattr(args, 'bin_qual', None) is not None:
+        if args.decode: error('ERROR: --bin-qual changes the qualities an encode stores: the text --decode writes is what the container holds')
+        bin_qual_table(args.bin_qual)
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     return args
+
+
+def bin_qual_table(spec):
+    """--bin-qual SPEC -> (the 256-byte table, the explicit form of the spec); a bad spec is this module's UqError (run as a script, this
+    module is `__main__` and uq_amd.binqual raises the class of `uq_amd.uq`)."""
+    from . import binqual
+    try:
+        return binqual.parse(spec), binqual.explicit(spec)
+    except Exception as e:
+        if type(e).__name__ != 'UqError': raise
+        error(str(e))
 
 
 def npy_header(shape, fortran_order, dtype):
@@ -248,15 +264,18 @@ class Session:
         ops, ctx, args = self.ops, self.ctx, self.args
         self.d_buf = d_buf
         if not hasattr(self, '_host'): self.path, self._host = None, None
+        binned = self.bin_qualities(census) if getattr(args, 'bin_qual', None) is not None else None      # (line count, record index)
+        if binned is not None: census = None             # (its census has been closed; the step below runs its own: one more census per encode, with the flag only)
         if getattr(self, 'index_only', False):           # --fingerprint: the line count and (on first use) the record index, no statistics, no pack
             self._spec, self._fq, self._d_ls, self.load_path = None, None, None, 'index only'
-            nlines = census.end() if census is not None else ops.count_lines(ctx, d_buf)
+            if binned is not None: nlines, self._d_ls = binned
+            else: nlines = census.end() if census is not None else ops.count_lines(ctx, d_buf)
             if nlines % 4 != 0:
                 error('ERROR: The FASTQ file provided contains' + str(nlines) + 'rows, which is not divisible by 4!')
             if nlines == 0: error('ERROR: empty input')
             self.total = nlines // 4
             return
-        self._spec, self._fq, self._d_ls, self.load_path = None, None, None, 'multi-pass'
+        self._spec, self._fq, self._d_ls, self.load_path = None, None, None if binned is None else binned[1], 'multi-pass'
         self._guess_shared = False
         nbytes = int(d_buf.numel())
         nlines, queued, guess, cap = None, None, None, 0
@@ -320,6 +339,28 @@ class Session:
             self.d_stats = ops.stats_new(ctx)
             ops.stats_accumulate(ctx, self.d_stats, self.d_buf, self.d_ls, 0, self.total)
 
+    binned_changed = 0         # --bin-qual: quality characters this session's binning changed
+
+    def bin_qualities(self, census=None):
+        """--bin-qual, at the head of load_device: the table of the spec applied to every quality line of self.d_buf, in place
+        (uq_requantise_qualities), before the head guess, the statistics, the pack or a fingerprint see the text -- every path works on the
+        binned stream only.  Needs the record index (the census, closed here if load() had begun one, + uq_index_lines); newlines do not
+        move, so the index stays valid and is handed back: (line count, index); the index is None, and nothing is binned, when the lines
+        are not whole records (load_device reports that)."""
+        ops, ctx = self.ops, self.ctx
+        d_buf = self.d_buf
+        lut, self.bin_qual_ranges = bin_qual_table(self.args.bin_qual)
+        nlines = census.end() if census is not None else (ops.count_lines(ctx, d_buf) if d_buf.numel() else 0)
+        if nlines == 0 or nlines % 4 != 0: return nlines, None
+        ls = ops.index_lines(ctx, d_buf, nlines)
+        d_changed = ops.changed_new(ctx)
+        ops.requantise_qualities(ctx, d_buf, ls, 0, nlines // 4, lut, d_changed)
+        self.binned_changed = int(ctx.to_numpy(d_changed).view(np.uint64)[0])
+        return nlines, ls
+
+    def binned_changed_in_file(self):
+        return self.binned_changed
+
     # the fused QNAME pass's seams (the sharded session overrides the last two: rank 0's guess is every rank's)
     def fused_qname_enabled(self):
         return not getattr(self.args, 'multi_pass', False) and not getattr(self.args, 'host_qname', False) and not getattr(self.args, 'exact_qname', False)
@@ -345,6 +386,8 @@ class Session:
     @property
     def host(self):
         """Host copy of the FASTQ bytes: only the sequential QNAME fallback needs it."""
+        # (under --bin-qual the file still holds the qualities as given while d_buf holds the binned ones: this copy is read for its QNAME
+        # lines only, which binning does not touch)
         if self._host is None:
             self._host = np.fromfile(self.path, dtype=np.uint8) if self.path else self.ctx.to_numpy(self.d_buf)
         return self._host
@@ -407,6 +450,11 @@ class Session:
             error(str(e))
         self.columns = columns
         self.qname_arrays = arrays
+        binning = None
+        if getattr(args, 'bin_qual', None) is not None:
+            binning = {'spec': args.bin_qual, 'ranges': getattr(self, 'bin_qual_ranges', None) or bin_qual_table(args.bin_qual)[1],
+                       'changed': self.binned_changed_in_file()}
+            self.say('Binned qualities (%s): %d of %d quality characters changed' % (args.bin_qual, binning['changed'], sum(d['qual_distribution'].values())))
         self.report(prefix, suffix, separators)
         self.config = {
             'base_distribution': d['base_distribution'], 'qual_distribution': d['qual_distribution'],
@@ -415,6 +463,7 @@ class Session:
             'bits_per_quality': d['bits_per_quality'], 'N_qual': d['N_qual'], 'dna_max': d['dna_max'],
             'QNAME_prefix': prefix, 'QNAME_suffix': suffix, 'QNAME_separators': separators, 'QNAME_columns': columns,
         }
+        if binning is not None: self.config['quality_binning'] = binning
 
     def report(self, prefix, suffix, separators):
         """The analysis printout of uq.py:459-545 (condensed: same facts, fewer bar charts)."""
@@ -852,6 +901,8 @@ class Session:
                 args.output, want['reads'], 'as a multiset, resorted by --sort ' + args.sort if resorted else 'in the same order',
                 key + ' fingerprint equal', hx(got['records']))
             if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
+            if getattr(args, 'bin_qual', None) is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
+                line += '; qualities binned by --bin-qual %s, %d characters changed' % (args.bin_qual, self.binned_changed_in_file())
             show(line)
             return True
         show('VERIFY FAILED: %s does not decode to the reads of %s (%s %s, decoded %s)' % (args.output, args.input, key, hx(want[key]), hx(got[key])))
