@@ -125,7 +125,7 @@ __device__ __forceinline__ void store_tile(uint8_t* gdst, uint8_t* lsrc, uint32_
 // layout (qname_fused.hip: prefix = line1[:plen], suffix = line1[l1len - slen:], ordered separators) and parse its fields
 // (uq.py:560-565 split, 724-726 int()): value of field c of read `row` -> vals[c * pitch + row].  Whatever does not conform
 // raises a flag (include/uqhip.h lists them); the host then runs the exact passes of qname_dev.hip instead.
-struct QnLds {
+struct alignas(16) QnLds {            // (a multiple of 16 bytes: the line offsets and the out tile follow it in the carve)
     uint8_t line1[256 + 16];        // zero padded: windows may read past the line
     uint8_t inset[256];
     uint8_t seps[32];
@@ -253,6 +253,7 @@ __device__ __forceinline__ void qname_tile(const uint8_t* stage, const uint32_t*
 
 constexpr int PK_NV = 5;   // 16-byte loads per lane per tile: a tile spans at most PK_NV * 256 * 16 = 20 KiB
 constexpr int PK_NV_STATS = 4;   // the fused pack + statistics kernel keeps a few KiB of LDS for its count table: 16 KiB tiles, same occupancy
+constexpr uint32_t pk_stage_bytes(bool stats) { return (uint32_t)(stats ? PK_NV_STATS : PK_NV) * PK_THREADS * 16 + 32; }   // the staging region: what the lanes hold in flight, and slack for the windows
 // Its counts are taken on the CODES the lookup-free conversion has just produced (bin = base code << 6 | quality code: two
 // instructions per four pairs instead of re-deriving bins from the characters), into an LDS table (3-bit bases: four copies);
 // code 0 fill pairs of a read's partial top group and the N-trick positions (counted as their substitute there) are taken off
@@ -278,6 +279,10 @@ constexpr uint32_t pks_words(int bd, bool four_wg) { return pks_bins(bd) * pks_c
 // with dependent loads there stalls on the tile's bytes requested just before it: 1.62 -> 1.94 ms).
 // start of the tile's first record; T = census tile of the newline in front of it, A = its slot + 1 | newlines of T << 16, B = newlines of T + 1 | of T + 2 << 16
 struct TileRec { uint64_t start; uint32_t T, A, B, pad; };
+// What the tile loop never reads -- the addresses the epilogue reports to, what only a tile taken piece by piece needs -- waits in LDS in the forms built
+// for four workgroups per CU: held in uniform registers over the loop it is spilled to vector lanes and moved back and forth by every tile.
+// (Not the census's offsets: a pointer read back from LDS is a generic one, and the loads through it would be flat loads.)
+struct PkParked { unsigned long long* bad; uq_stats* st; uq_qname_fused* qf; uint64_t first, nb, nl_total; uint32_t Rs, pad; };
 struct PackLists {
     CensusView cv;                             // cv.list == nullptr: the expanded index (`ls`) is used
     const uint32_t* over;                      // the census's overflow word: a tile held more newlines than its list (the lists are not usable)
@@ -313,7 +318,7 @@ __global__ __launch_bounds__(256) void tile_origin_kernel(CensusView cv, const u
     rec[tt] = out;
 }
 
-// LDS carve (dynamic): [16 B guard][stage][out_d | out_q][meta u32 x (4R+4)][luts 3 x 512 B]
+// LDS carve (dynamic): [16 B guard][stage][luts 3 x 512 B][QnLds (STATS)][meta u32 x (4R+4)][out_d | out_q]
 // Workgroups are persistent: each walks tiles b, b + S, b + 2S, ... with a software pipeline -- the
 // next tile's bytes and line offsets are loaded into registers (in flight) while the current tile is
 // packed out of LDS; span bounds are requested two tiles ahead.
@@ -339,12 +344,15 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                                                                const TileRec* __restrict__ trec) {      // trec: [pack tiles + 1] with pl (a restrict parameter of its own: the records are read through the scalar cache, like `ls`)
     constexpr int NV = STATS ? PK_NV_STATS : PK_NV;
     extern __shared__ __align__(16) uint8_t smem[];
+    // (everything in front of the out tile sits at an offset the compiler knows: one uniform address to hold over the tile loop instead of five)
+    constexpr uint32_t STAGE_BYTES = pk_stage_bytes(STATS);      // = g.stage_bytes
     uint8_t* stage = smem + 16;                       // reads of up to 8 bytes below offset 0 stay in bounds
-    uint8_t* out_d = stage + g.stage_bytes;
-    uint32_t* meta = (uint32_t*)(out_d + g.out_bytes);
-    int16_t* l_dna = (int16_t*)(meta + 4 * g.R + 4);
+    int16_t* l_dna = (int16_t*)(stage + STAGE_BYTES);
     int16_t* l_qual = l_dna + 256;
     int16_t* l_nq = l_qual + 256;
+    QnLds* qn = (QnLds*)(l_nq + 256);                            // the QNAME phase's state (uq_pack_stats_qname only)
+    uint32_t* meta = (uint32_t*)((uint8_t*)qn + (STATS ? sizeof(QnLds) : 0));
+    uint8_t* out_d = (uint8_t*)(meta + 4 * g.R + 4);
 
     const uint32_t tid = threadIdx.x;
     l_dna[tid] = lut.dna_code[tid];
@@ -359,7 +367,6 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     constexpr uint32_t PKS_BINS = pks_bins(BD), PKS_WORDS = pks_words(BD, FOUR_WG);
     if (STATS) for (uint32_t i = tid; i < PKS_WORDS; i += PK_THREADS) cnt_tab[i] = 0;       // the first tile's barrier orders it
     if (VAR) for (uint32_t i = tid; i < (g.out_bytes >> 4); i += PK_THREADS) ((uint4*)out_d)[i] = make_uint4(0, 0, 0, 0);       // (likewise; every copy-out clears what it reads)
-    QnLds* qn = (QnLds*)(l_nq + 256);                            // the QNAME phase's state (uq_pack_stats_qname only)
     bool qn_on = false;
     if (STATS && QN) qn_on = qf->ok != 0;                        // the guess kernels in front may have declined: the lines are left alone
     if (STATS && QN) {
@@ -382,19 +389,36 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
             for (uint32_t k = 0; k < 10; ++k) { qn->pow10[k] = pw; pw *= 10; }
         }
     }
+    // Reads and tiles are counted in 32 bits (pack_impl refuses more reads than that in one call): half the uniform registers the tile loop
+    // holds.  Byte offsets -- r0 * Cd, positions in the stream -- are formed in 64 bits where they are used.
+    uint32_t nr = (uint32_t)n;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(nr));                               // (a register of its own: without this the compiler holds -- and spills -- `first` and `n` as the four registers it loaded them into)
+#endif
     uint64_t nl_total = 4 * (first + n);              // (list form: closes the last census tile's list)
     constexpr bool lists = STATS && LISTS;            // (instances of their own: a run-time choice between `ls` and `trec` turns the tile bounds' scalar loads into vector
                                                       // loads that wait for the tile's stores -- and spills the kernels built for five workgroups per CU)
     if (d_async) {                                    // the queued form (uq_pack_stats_async): the census in front left the line count on the device;
         nl_total = d_async[0];
         const uint64_t have = d_async[0] / 4;         // `n` is what the tables hold
-        if (have > n) incomplete = true; else n = have;
-        if (d_async[1] || (lists && *pl.over)) { incomplete = true; n = 0; }   // the queued index in front gave up (list or capacity overflow): its entries are not line starts
+        if (have > nr) incomplete = true; else nr = (uint32_t)have;
+        if (d_async[1] || (lists && *pl.over)) { incomplete = true; nr = 0; }   // the queued index in front gave up (list or capacity overflow): its entries are not line starts
     }
 
-    const uint64_t R = g.R;
-    const uint64_t ntiles = (n + R - 1) / R;
-    const uint64_t S = gridDim.x;
+    __shared__ PkParked parked;                       // (FOUR_WG only: the others never touch it, and it takes no LDS there)
+    if constexpr (FOUR_WG) {
+        if (tid == 0) { parked.bad = bad; parked.st = st; parked.qf = qf; parked.first = first; parked.nb = pl.cv.nb; parked.nl_total = nl_total; parked.Rs = g.Rs; }
+    }                                                 // (the first tile's barrier orders it)
+    auto p_bad = [&] { if constexpr (FOUR_WG) return parked.bad; else return bad; };
+    auto p_st = [&] { if constexpr (FOUR_WG) return parked.st; else return st; };
+    auto p_qf = [&] { if constexpr (FOUR_WG) return parked.qf; else return qf; };
+    auto p_first = [&] { if constexpr (FOUR_WG) return parked.first; else return first; };
+    auto p_nl_total = [&] { if constexpr (FOUR_WG) return parked.nl_total; else return nl_total; };
+    auto p_Rs = [&] { if constexpr (FOUR_WG) return parked.Rs; else return g.Rs; };
+    auto p_cv = [&] { CensusView v = pl.cv; if constexpr (FOUR_WG) v.nb = parked.nb; return v; };
+    const uint32_t R = g.R;
+    const uint32_t ntiles = (nr + R - 1) / R;
+    const uint32_t S = gridDim.x;
     struct Bounds { uint64_t g0, g1; uint32_t pT, pA, pB; };       // pT, pA, pB: PackLists::place
     struct Regs { uint4 v[NV]; uint64_t m0; uint64_t g0; uint32_t skew, nvec, Rt, mrel, mraw; bool ok; };      // (lists: line start - g0 + skew = mrel + mraw)
     // The bounds of a tile two steps ahead are requested by VECTOR loads, a dword (or an index entry) a lane, and put together with v_readlane when the tile's
@@ -402,21 +426,21 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     // spot: the kernel is short of SGPRs, the loaded values went straight to VGPR lanes, and every tile began with a round trip to the L2.  A vector load waits
     // behind phase C's `vmcnt(0)`, a whole tile later.)
     struct RawBounds { uint32_t lo, hi; };
-    auto load_raw = [&](uint64_t tt) {
+    auto load_raw = [&](uint32_t tt) {
         RawBounds x{0u, 0u};
         if (tt < ntiles) {
             const uint32_t ln = lane_id();
             if constexpr (lists) {                // lanes 0 .. 7: the six dwords of the tile's record and the two of the next record's start
                 x.lo = ((const uint32_t*)(trec + tt))[ln < 8u ? ln : 0u];
             } else {
-                const uint32_t Rn = (uint32_t)((n - tt * R) < R ? (n - tt * R) : R);
-                const uint64_t v = ls[4 * (first + tt * R) + (ln == 1u ? 4 * Rn : 0u)];           // lane 0: the tile's start, lane 1: its end
+                const uint32_t Rn = (nr - tt * R) < R ? (nr - tt * R) : R;
+                const uint64_t v = ls[4 * (first + (uint64_t)tt * R) + (ln == 1u ? 4 * Rn : 0u)];           // lane 0: the tile's start, lane 1: its end
                 x.lo = (uint32_t)v; x.hi = (uint32_t)(v >> 32);
             }
         }
         return x;
     };
-    auto bounds_of = [&](uint64_t tt, const RawBounds& x) {
+    auto bounds_of = [&](uint32_t tt, const RawBounds& x) {
         auto lane = [](uint32_t v, int k) { return (uint32_t)__builtin_amdgcn_readlane((int)v, k); };       // (the builtin returns int: without the cast a set bit 31 -- an offset beyond 2 GiB -- would be sign-extended into the upper half)
         Bounds b{0, 0, 0, 0, 0};
         if (tt < ntiles) {
@@ -431,21 +455,21 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         }
         return b;
     };
-    auto load_bounds = [&](uint64_t tt) {
+    auto load_bounds = [&](uint32_t tt) {
         Bounds b{0, 0, 0, 0, 0};
         if (tt < ntiles) {
-            const uint32_t Rn = (uint32_t)((n - tt * R) < R ? (n - tt * R) : R);
+            const uint32_t Rn = (nr - tt * R) < R ? (nr - tt * R) : R;
             if constexpr (lists) {                // (one round trip: the two records side by side)
                 const TileRec r0 = trec[tt];
                 b.g0 = r0.start; b.pT = r0.T; b.pA = r0.A; b.pB = r0.B; b.g1 = trec[tt + 1].start;
             }
-            else { b.g0 = ls[4 * (first + tt * R)]; b.g1 = ls[4 * (first + tt * R) + 4 * Rn]; }
+            else { b.g0 = ls[4 * (first + (uint64_t)tt * R)]; b.g1 = ls[4 * (first + (uint64_t)tt * R) + 4 * Rn]; }
         }
         return b;
     };
-    auto tile_reads = [&](uint64_t tt) -> uint32_t { return tt < ntiles ? (uint32_t)((n - tt * R) < R ? (n - tt * R) : R) : 0u; };
+    auto tile_reads = [&](uint32_t tt) -> uint32_t { return tt < ntiles ? ((nr - tt * R) < R ? (nr - tt * R) : R) : 0u; };
     // request the bytes and line offsets of reads [rfirst, rfirst + cnt) (their span is b); not ok = the span does not fit the stage
-    auto issue = [&](uint64_t rfirst, uint32_t cnt, Bounds b) {
+    auto issue = [&](uint32_t rfirst, uint32_t cnt, Bounds b) {
         Regs x;
         x.ok = false; x.m0 = 0; x.g0 = b.g0; x.skew = 0; x.nvec = 0; x.Rt = 0; x.mrel = 0; x.mraw = 0;
 #pragma unroll
@@ -456,7 +480,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         x.skew = (uint32_t)(((uint64_t)(uintptr_t)buf + b.g0) - a0);
         const uint64_t span = b.g1 - b.g0 + x.skew;
         x.nvec = (uint32_t)((span + 15) >> 4);
-        x.ok = span + 32 <= g.stage_bytes && x.nvec <= (uint32_t)(NV * PK_THREADS);
+        x.ok = span + 32 <= STAGE_BYTES && x.nvec <= (uint32_t)(NV * PK_THREADS);
         if constexpr (lists) {                   // the tile's 4 Rt + 1 newlines within the three census tiles the place describes?
             const uint32_t kk = b.pA & 0xFFFFu, avail = (b.pA >> 16) + (b.pB & 0xFFFFu) + (b.pB >> 16);
             if (kk + 4 * cnt > avail) x.ok = false;         // (lines of many KiB: the tile goes piece by piece, each with its own search)
@@ -475,7 +499,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                 // with it for the tile's bytes requested above
                 x.mrel = x.skew - (uint32_t)b.g0 + (idx == 0 ? 0u : (uint32_t)t * (uint32_t)CV_TILE - pl.cv.mis + 1u);      // (modulo 2^32: a tile spans less)
                 x.mraw = idx == 0 ? 0u : (uint32_t)pl.cv.list[(uint64_t)t * CV_LIST_CAP + (idx - 1)];
-            } else x.m0 = ls[4 * (first + rfirst) + tid];
+            } else x.m0 = ls[4 * (first + (uint64_t)rfirst) + tid];
         }
         return x;
     };
@@ -483,9 +507,9 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     uint32_t rr, pp;                                  // this lane packs groups pp, pp + P, ... of read rr of every tile
     fast_divmod(tid, g.P, g.magicP, rr, pp);
     uint32_t badr = 0xFFFFFFFFu;
-    uint64_t bad_tile = UQ_NONE;
+    uint32_t bad_tile = 0xFFFFFFFFu;
     // one tile: registers -> LDS (A), `between()` (the caller's prefetch of the next tile), pack (B), store (C)
-    auto do_tile = [&](const uint64_t r0, const Regs& cur, auto&& between) {
+    auto do_tile = [&](const uint32_t r0, const Regs& cur, auto&& between) {
         const uint32_t Rt = cur.Rt;
         uint8_t* out_q = out_d + ((Rt * g.Cd + 15) & ~15u);
         // ---- A: registers -> LDS
@@ -496,7 +520,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         } else {
             if (tid == 0) bad_tile = bad_tile < r0 ? bad_tile : r0;
             incomplete = true;
-            if (STATS && QN && qn_on && tid == 0) atomicOr(&qf->flags, 256u);
+            if (STATS && QN && qn_on && tid == 0) atomicOr(&p_qf()->flags, 256u);
         }
         __syncthreads();
         const bool ok = cur.ok;
@@ -504,7 +528,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         // the QNAME lines of the tile: the last wave, a lane per read (its lanes have no part in phase B: P is sized for three waves)
 #ifndef PK_ABL_NOQN
         if (STATS && QN && qn_on && ok && tid >= PK_THREADS - 64 && tid - (PK_THREADS - 64) < Rt)
-            qname_tile(stage, meta, tid - (PK_THREADS - 64), qn, qvals, qpitch, r0 + (tid - (PK_THREADS - 64)));
+            qname_tile(stage, meta, tid - (PK_THREADS - 64), qn, qvals, qpitch, (uint64_t)r0 + (tid - (PK_THREADS - 64)));
 #endif
         if (ok) {
             // ---- B: P lanes per read; a lane owns groups of 8 consecutive symbols, both streams:
@@ -616,7 +640,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                         aq[k >> 2] = (aq[k >> 2] << BQ) | (uint32_t)qc;
                     }
                     if (orall < 0) {            // a character without a code: report, keep the row deterministic
-                        badr = badr < (uint32_t)(r0 + r) ? badr : (uint32_t)(r0 + r);
+                        badr = badr < r0 + r ? badr : r0 + r;
                         ad[0] = ad[1] = aq[0] = aq[1] = 0;
                     }
                     ad0 = ad[0]; ad1 = ad[1]; aq0 = aq[0]; aq1 = aq[1];
@@ -662,7 +686,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
 #endif
                     if (L > g.dna_max || Lq != L) incomplete = true;        // symbols this kernel does not visit
                 }
-                if (L > g.dna_max || meta[4 * r + 4] - qo - 1 != L) { badr = badr < (uint32_t)(r0 + r) ? badr : (uint32_t)(r0 + r); L = 0; }
+                if (L > g.dna_max || meta[4 * r + 4] - qo - 1 != L) { badr = badr < r0 + r ? badr : r0 + r; L = 0; }
                 uint8_t* orow_d = out_d + r * g.Cd + (g.Cd - 1);
                 uint8_t* orow_q = out_q + r * g.Cq + (g.Cq - 1);
                 // VAR: only the groups that hold a symbol or the sentinel -- the rows' empty upper parts are zero already: every copy-out clears what
@@ -687,22 +711,22 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         if (ok) {
             // ---- C: coalesced stores of the two packed tiles (widest vector the tile's byte offset allows)
             if constexpr (STATS && (NTRICK || QN)) {            // (the forms built for four workgroups per CU have the registers for the inline loop)
-                store_tile<VAR>(dna + r0 * g.Cd, out_d, Rt * g.Cd, tid);
-                store_tile<VAR>(qual + r0 * g.Cq, out_q, Rt * g.Cq, tid);
+                store_tile<VAR>(dna + (uint64_t)r0 * g.Cd, out_d, Rt * g.Cd, tid);
+                store_tile<VAR>(qual + (uint64_t)r0 * g.Cq, out_q, Rt * g.Cq, tid);
             } else {
-                store_tile_any<VAR>(dna + r0 * g.Cd, out_d, Rt * g.Cd, tid);
-                store_tile_any<VAR>(qual + r0 * g.Cq, out_q, Rt * g.Cq, tid);
+                store_tile_any<VAR>(dna + (uint64_t)r0 * g.Cd, out_d, Rt * g.Cd, tid);
+                store_tile_any<VAR>(qual + (uint64_t)r0 * g.Cq, out_q, Rt * g.Cq, tid);
             }
         }
     };
 
-    uint64_t t = blockIdx.x;
+    uint32_t t = blockIdx.x;
     // (only the forms built for four workgroups per CU take the vector loads: at the 96 registers of the others they spill -- 27 dwords in the indexed
     // pack + statistics kernel, 1.40 -> 1.50 ms -- and those keep the scalar loads, requested at the top of the tile before)
     constexpr bool VBOUNDS = STATS && (NTRICK || QN);
     using NextBounds = std::conditional_t<VBOUNDS, RawBounds, Bounds>;
-    auto fetch_next = [&](uint64_t tt) -> NextBounds { if constexpr (VBOUNDS) return load_raw(tt); else return load_bounds(tt); };
-    auto next_bounds = [&](uint64_t tt, const NextBounds& x) -> Bounds { if constexpr (VBOUNDS) return bounds_of(tt, x); else return x; };
+    auto fetch_next = [&](uint32_t tt) -> NextBounds { if constexpr (VBOUNDS) return load_raw(tt); else return load_bounds(tt); };
+    auto next_bounds = [&](uint32_t tt, const NextBounds& x) -> Bounds { if constexpr (VBOUNDS) return bounds_of(tt, x); else return x; };
     NextBounds b_next = fetch_next(t + S);
     Regs cur = issue(t * R, tile_reads(t), load_bounds(t));
 #ifndef PK_NO_EARLY_WAIT
@@ -721,23 +745,27 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
             // the tile's records add up to more than the stage holds (R comes from the average record length): pack it in
             // pieces of g.Rs reads, which always fit, one after the other; then pick the pipeline up again
             const uint32_t Rt = cur.Rt;
-            for (uint32_t sub = 0; sub < Rt; sub += g.Rs) {
-                const uint32_t cnt = Rt - sub < g.Rs ? Rt - sub : g.Rs;
-                const uint64_t rf = t * R + sub;
+            __syncthreads();                          // (the very first tile may come here: no barrier has ordered `parked` yet)
+            const uint32_t Rs = p_Rs();
+            for (uint32_t sub = 0; sub < Rt; sub += Rs) {
+                const uint32_t cnt = Rt - sub < Rs ? Rt - sub : Rs;
+                const uint32_t rf = t * R + sub;
                 Bounds sb{0, 0, 0, 0, 0};
                 if constexpr (lists) {                  // (rare: a search per piece, and the counts of its three census tiles)
                     uint32_t T, kk; bool found;
-                    cv_locate(pl.cv, (int64_t)(4 * (first + rf)) - 1, T, kk);
-                    sb.g0 = cv_line_start(pl.cv, nl_total, T, kk, 0, found); sb.g1 = cv_line_start(pl.cv, nl_total, T, kk, 4 * cnt, found);
+                    const CensusView cv = p_cv();
+                    const uint64_t nl_total = p_nl_total();
+                    cv_locate(cv, (int64_t)(4 * (p_first() + rf)) - 1, T, kk);
+                    sb.g0 = cv_line_start(cv, nl_total, T, kk, 0, found); sb.g1 = cv_line_start(cv, nl_total, T, kk, 4 * cnt, found);
                     uint32_t c[3];
 #pragma unroll
                     for (uint32_t k = 0; k < 3; ++k) {
                         const uint64_t tq = (uint64_t)T + k;
-                        c[k] = tq < pl.cv.nb ? (uint32_t)((tq + 1 < pl.cv.nb ? (uint64_t)pl.cv.offs[tq + 1] : nl_total) - pl.cv.offs[tq]) : 0u;
+                        c[k] = tq < cv.nb ? (uint32_t)((tq + 1 < cv.nb ? (uint64_t)cv.offs[tq + 1] : nl_total) - cv.offs[tq]) : 0u;
                         if (c[k] > CV_LIST_CAP) c[k] = CV_LIST_CAP;
                     }
                     sb.pT = T; sb.pA = kk | (c[0] << 16); sb.pB = c[1] | (c[2] << 16);
-                } else { sb.g0 = ls[4 * (first + rf)]; sb.g1 = ls[4 * (first + rf) + 4 * cnt]; }
+                } else { sb.g0 = ls[4 * (first + (uint64_t)rf)]; sb.g1 = ls[4 * (first + (uint64_t)rf) + 4 * cnt]; }
                 const Regs piece = issue(rf, cnt, sb);
                 do_tile(rf, piece, [] {});
                 __syncthreads();                      // the next piece overwrites the stage and the out tile
@@ -750,8 +778,8 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         }
     }
     // (*bad is UQ_NONE when this kernel starts: set by tile_origin_kernel in front of it with the census's lists, else by pack_impl's clear)
-    if (badr != 0xFFFFFFFFu) atomicMin(bad, (unsigned long long)badr);
-    if (bad_tile != UQ_NONE) atomicMin(bad, (unsigned long long)bad_tile);
+    if (badr != 0xFFFFFFFFu) atomicMin(p_bad(), (unsigned long long)badr);
+    if (bad_tile != 0xFFFFFFFFu) atomicMin(p_bad(), (unsigned long long)bad_tile);
     if (STATS) {
         // fills were counted as (code 0, code 0), N-trick positions as (code 0, n_code): take them off their bins (any copy: the
         // flush sums the copies modulo 2^32)
@@ -762,6 +790,8 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         }
         __syncthreads();
         const uint32_t qmin = 0x80u - (g.q_addlo & 0xFFu);
+        uq_stats* const st = p_st();
+        uq_qname_fused* const qf = p_qf();
         for (uint32_t bin = tid; bin < PKS_BINS; bin += PK_THREADS) {
             uint32_t v = 0;
 #pragma unroll
@@ -775,12 +805,12 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
             const uint32_t v = cnt_tab[PKS_BINS * PKS_COPIES];
             if (v) atomicAdd((unsigned long long*)&st->counts[(g.n_char & 0xFFu) * 256 + (g.n_qchar & 0xFFu)], (unsigned long long)v);
         }
-        acc.flush(st, first);
+        acc.flush(st, p_first());
         if (incomplete) st->reserved = 1;
         if (QN) {                                            // (the barrier above also closes the last tile's QNAME phase)
             if (qn_on && tid < UQ_QF_MAXC && qn->vmin[tid] <= qn->vmax[tid]) { atomicMin(&qf->vmin[tid], qn->vmin[tid]); atomicMax(&qf->vmax[tid], qn->vmax[tid]); }
             if (qn_on && tid == 0 && qn->flags) atomicOr(&qf->flags, qn->flags);
-            if (blockIdx.x == 0 && tid == 0) qf->nreads = n;
+            if (blockIdx.x == 0 && tid == 0) qf->nreads = nr;
         }
     }
 }
@@ -874,6 +904,9 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
                      uint32_t* d_vals = nullptr, uint64_t vals_pitch = 0) {
     // d_line_start == nullptr (queued forms only): the line starts come from the lists of the census queued in front (lines.h)
     const bool use_lists = d_line_start == nullptr && d_async != nullptr && d_stats != nullptr;
+    // (first of all, before anything is touched or queued: the kernels count reads and tiles in 32 bits; row ids are uint32 throughout the
+    // container, so no caller has more in a shard)
+    UQ_REQUIRE(nreads <= (1ull << 31), "uq_pack: %llu reads in one call (at most 2^31)", (unsigned long long)nreads);
     UQ_REQUIRE(ctx && d_buf && (d_line_start || use_lists) && hp && d_dna && d_qual && d_bad, "uq_pack: null argument");
     UQ_REQUIRE(!use_lists || (ctx->async_buf == d_buf && ctx->async_nbytes > 0), "uq_pack_stats_async: no line index given and no census of this buffer queued in front");
     if (h_fused) *h_fused = 0;
@@ -962,7 +995,7 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
     if (R == 0) R = 1;
     if (Rs > R) Rs = R;
     g.R = R; g.Rs = Rs;
-    g.stage_bytes = stage_cap + 32;
+    g.stage_bytes = pk_stage_bytes(d_stats != nullptr);         // (= stage_cap + 32; the kernels take it as a constant)
     g.out_bytes = (((R * Cd + 15) & ~15u) + R * Cq + 15) & ~15u;
     // phase B: P lanes per read
     uint32_t P = (d_q ? PK_THREADS - 64 : PK_THREADS) / R;        // (QN: the last wave parses QNAME lines instead)
@@ -1019,7 +1052,7 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
         return 0;
     }
     const bool var_deal = d_stats && use_lists && hp->variable;
-    const size_t lds_static = d_stats ? pks_words((int)bd, ntrick || d_q != nullptr) * 4 : 4;        // the kernels' count table
+    const size_t lds_static = d_stats ? pks_words((int)bd, ntrick || d_q != nullptr) * 4 + ((ntrick || d_q != nullptr) ? ((sizeof(PkParked) + 15) & ~size_t(15)) : 0) : 4;        // the kernels' count table (and what they park beside it)
     const size_t lds = 16 + (size_t)g.stage_bytes + g.out_bytes + (4 * R + 4) * 4 + 3 * 512 + (d_stats ? sizeof(QnLds) : 0);
     UQ_REQUIRE(lds + lds_static <= 160 * 1024, "uq_pack: tile needs %zu bytes of LDS", lds + lds_static);
     const uint64_t tiles = (nreads + R - 1) / R;
