@@ -26,6 +26,26 @@
 #include "lines.h"
 #include "histo.h"
 
+// PK_ROLE_CLOCK (a variant build: tools/variants.sh pack.hip clock -DPK_ROLE_CLOCK; tools/pack_roles.py reads it): every wave of pack_tile_kernel reads the
+// cycle counter at five points of a tile -- (1) behind barrier 1, (2) arriving at barrier 2, (3) behind it, (4) behind the wait for the next tile's
+// bytes, (5) behind the copy-out -- and sums the intervals in registers; at the end the sums are added, per role (0: a wave that packs, 1: the QNAME
+// parser's wave), to pk_role_clock[role][0..4] = phase A and barrier 1, phase B, wait at barrier 2, wait for the next tile, phase C; [5] tiles, [6] waves.
+// (The counter is read through the scalar cache and shares a wait counter with the LDS: the clocked kernel is slower than the plain one, 1.74 against 1.46 ms.)
+#ifdef PK_ROLE_CLOCK
+__device__ unsigned long long pk_role_clock[16];
+#define PK_CLOCK(k) do { const uint64_t now_ = __builtin_readcyclecounter(); ck_sum[(k) - 1] += now_ - ck_prev; ck_prev = now_; if ((k) == 1) ++ck_tiles; } while (0)
+extern "C" int uq_pack_role_clock(unsigned long long* out16, int reset) {
+    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(pk_role_clock), sizeof(pk_role_clock)) != hipSuccess) return 1;
+    if (reset) {
+        const unsigned long long zero[16] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(pk_role_clock), zero, sizeof(zero)) != hipSuccess) return 1;
+    }
+    return 0;
+}
+#else
+#define PK_CLOCK(k) do { } while (0)
+#endif
+
 namespace {
 constexpr int PK_THREADS = 256;
 
@@ -508,6 +528,10 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     fast_divmod(tid, g.P, g.magicP, rr, pp);
     uint32_t badr = 0xFFFFFFFFu;
     uint32_t bad_tile = 0xFFFFFFFFu;
+#ifdef PK_ROLE_CLOCK
+    uint64_t ck_prev = 0, ck_sum[5] = {0, 0, 0, 0, 0};
+    uint32_t ck_tiles = 0;
+#endif
     // one tile: registers -> LDS (A), `between()` (the caller's prefetch of the next tile), pack (B), store (C)
     auto do_tile = [&](const uint32_t r0, const Regs& cur, auto&& between) {
         const uint32_t Rt = cur.Rt;
@@ -524,11 +548,21 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         }
         __syncthreads();
         const bool ok = cur.ok;
+        PK_CLOCK(1);
+        // The parser's wave reaches barrier 2 last -- the three waves that pack wait there for 15 % of a tile (tools/pack_roles.py) -- although it
+        // issues fewer instructions than they do: it shares its SIMD with three packing waves of the CU's other workgroups, which have that time to spare.
+        // From barrier 1 until its lines are parsed it asks for the SIMD's issue slots first (PK_QN_NO_PRIO: as before; 1.42 -> 1.37 ms).
+#ifndef PK_QN_NO_PRIO
+        if (STATS && QN && tid >= PK_THREADS - 64) __builtin_amdgcn_s_setprio(3);
+#endif
         between();
         // the QNAME lines of the tile: the last wave, a lane per read (its lanes have no part in phase B: P is sized for three waves)
 #ifndef PK_ABL_NOQN
         if (STATS && QN && qn_on && ok && tid >= PK_THREADS - 64 && tid - (PK_THREADS - 64) < Rt)
             qname_tile(stage, meta, tid - (PK_THREADS - 64), qn, qvals, qpitch, (uint64_t)r0 + (tid - (PK_THREADS - 64)));
+#endif
+#ifndef PK_QN_NO_PRIO
+        if (STATS && QN && tid >= PK_THREADS - 64) __builtin_amdgcn_s_setprio(0);
 #endif
         if (ok) {
             // ---- B: P lanes per read; a lane owns groups of 8 consecutive symbols, both streams:
@@ -701,13 +735,16 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
 #endif
             }
         }
+        PK_CLOCK(2);
         __syncthreads();
+        PK_CLOCK(3);
 #ifndef PK_NO_EARLY_WAIT
         // The next tile's bytes were requested a whole phase B ago: wait for them HERE, before this tile's stores are issued.  vmcnt counts loads and
         // stores together, in issue order: the wait the compiler would put in front of the next tile's phase A also waits for the stores below to be
         // acknowledged (1 - 1.5 us under load, every tile); behind this one it has nothing left to wait for.
         __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt / lgkmcnt left alone
 #endif
+        PK_CLOCK(4);
         if (ok) {
             // ---- C: coalesced stores of the two packed tiles (widest vector the tile's byte offset allows)
             if constexpr (STATS && (NTRICK || QN)) {            // (the forms built for four workgroups per CU have the registers for the inline loop)
@@ -718,6 +755,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                 store_tile_any<VAR>(qual + (uint64_t)r0 * g.Cq, out_q, Rt * g.Cq, tid);
             }
         }
+        PK_CLOCK(5);
     };
 
     uint32_t t = blockIdx.x;
@@ -731,6 +769,9 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     Regs cur = issue(t * R, tile_reads(t), load_bounds(t));
 #ifndef PK_NO_EARLY_WAIT
     __builtin_amdgcn_s_waitcnt(0x0F70);          // (every path into a tile's phase A has waited for the tile's bytes: see phase C)
+#endif
+#ifdef PK_ROLE_CLOCK
+    ck_prev = __builtin_readcyclecounter();
 #endif
     for (; t < ntiles; t += S) {
         NextBounds b_nn{};
@@ -777,6 +818,13 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
 #endif
         }
     }
+#ifdef PK_ROLE_CLOCK
+    if (lane_id() == 0) {
+        unsigned long long* ck = pk_role_clock + (STATS && QN && tid >= PK_THREADS - 64 ? 8 : 0);
+        for (int k = 0; k < 5; ++k) atomicAdd(ck + k, (unsigned long long)ck_sum[k]);
+        atomicAdd(ck + 5, (unsigned long long)ck_tiles); atomicAdd(ck + 6, 1ull);
+    }
+#endif
     // (*bad is UQ_NONE when this kernel starts: set by tile_origin_kernel in front of it with the census's lists, else by pack_impl's clear)
     if (badr != 0xFFFFFFFFu) atomicMin(p_bad(), (unsigned long long)badr);
     if (bad_tile != 0xFFFFFFFFu) atomicMin(p_bad(), (unsigned long long)bad_tile);
