@@ -140,6 +140,35 @@ int uq_fingerprint_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t*
 int uq_fingerprint_host(const uint8_t* h_buf, const uint64_t* h_line_start,
                         uint64_t first_read, uint64_t nreads, uint64_t read_index_base, uq_fingerprint* h_fp);
 
+/* ---- the per-cycle quality control tables `uqqc1` (`--qc`; an extension: the reference says nothing about what a file holds; DESIGN.md
+ * section 24).  One flat array of u64 counters, C = ncycles, 1 <= C <= UQ_QC_MAX_CYCLES.  For a record with the sequence line s (length Ls)
+ * and the quality line u (length Lu), both without their '\n', each line taken at its own length:
+ *   cls(b):  A/a -> 0, C/c -> 1, G/g -> 2, T/t -> 3, N/n -> 4, every other byte -> 5
+ *   q(b):    clamp((int)b - 33, 0, 93); a byte outside 33 .. 126 is clamped and also counted in qual_out_of_range
+ *   row(p):  min(p, C) -- rows 0 .. C - 1 are exact cycles, row C is the tail and takes every position >= C
+ * The array, in this order:
+ *   [0 .. 8)                reads, bases = SUM Ls, qual_chars = SUM Lu, qual_out_of_range, len_mismatch = #records with Ls != Lu, three reserved words (0)
+ *   base_by_cycle[C + 1][6]   [row(p)][cls(s[p])] += 1 for every p < Ls
+ *   qual_by_cycle[C + 1][94]  [row(p)][q(u[p])] += 1 for every p < Lu
+ *   length_hist[C + 1]        [min(Ls, C)] += 1 per record
+ *   mean_qual_hist[94]        if Lu > 0: [floor(SUM_p q(u[p]) / Lu)] += 1
+ *   gc_hist[101]              if Ls > 0: [floor(100 * #{p : cls(s[p]) in {1, 2}} / Ls)] += 1
+ * uq_qc_words(C) = 8 + 100 (C + 1) + (C + 1) + 94 + 101, or 0 for an invalid C.  Every field is a sum over records: calls and shards add.
+ * SUM base_by_cycle = bases, SUM qual_by_cycle = qual_chars, SUM length_hist = reads.
+ * uq_qc_init zeroes d_qc[0, uq_qc_words(C)) (device, 8-byte aligned; queued on the context's stream).  uq_qc_accumulate ADDS the records
+ * [first_read, first_read + nreads) of d_buf (any alignment; d_line_start as uq_index_lines writes it; lines shorter than 2^32 bytes; 64-bit
+ * offsets) into d_qc: one read of the stream, nothing written but d_qc, nothing read back; nreads == 0 is a no-op.  uq_qc_host: the same,
+ * sequentially, on host memory (ADDS into h_qc; needs no GPU). */
+#define UQ_QC_MAX_CYCLES 1024u
+#define UQ_QC_NBASE 6u
+#define UQ_QC_NQUAL 94u
+uint64_t uq_qc_words(uint32_t ncycles);
+int uq_qc_init(uq_ctx* ctx, uint64_t* d_qc, uint32_t ncycles);
+int uq_qc_accumulate(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start,
+                     uint64_t first_read, uint64_t nreads, uint32_t ncycles, uint64_t* d_qc);
+int uq_qc_host(const uint8_t* h_buf, const uint64_t* h_line_start,
+               uint64_t first_read, uint64_t nreads, uint32_t ncycles, uint64_t* h_qc);
+
 /* ---- quality binning (`--bin-qual`; an extension: the reference stores the qualities it is given).  LOSSY by request:
  * a byte table applied to the quality lines of a FASTQ text before anything else looks at it.
  * uq_requantise_qualities applies lut[] to every byte of line 4 (the quality line, without its '\n') of the records

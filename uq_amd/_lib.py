@@ -139,6 +139,9 @@ SIGNATURES = {
     'uq_fingerprint_init': [_vp, _vp],
     'uq_fingerprint_accumulate': [_vp, _vp, _vp, _u64, _u64, _u64, _vp],
     'uq_fingerprint_host': [_vp, _vp, _u64, _u64, _u64, _P(Fingerprint)],
+    'uq_qc_init': [_vp, _vp, _u32],
+    'uq_qc_accumulate': [_vp, _vp, _vp, _u64, _u64, _u32, _vp],
+    'uq_qc_host': [_vp, _vp, _u64, _u64, _u32, _vp],
     'uq_requantise_qualities': [_vp, _vp, _vp, _u64, _u64, _vp, _vp],
     'uq_requantise_qualities_host': [_vp, _vp, _u64, _u64, _vp, _P(_u64)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
@@ -213,6 +216,11 @@ SIGNATURES = {
     'uq_deflate_size_host_l': [_vp, _u32, _vp, _u64, _P(_u64), _u32],
 }
 
+# the entry points that return a value, not a status: name -> (restype, argtypes)
+VALUE_SIGNATURES = {
+    'uq_qc_words': (_u64, [_u32]),
+}
+
 _lib = None
 MISSING = []
 
@@ -242,6 +250,14 @@ def load():
             continue
         fn.argtypes = args
         fn.restype = C.c_int
+    for name, (res, args) in VALUE_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            MISSING.append(name)
+            continue
+        fn.argtypes = args
+        fn.restype = res
     if lib.uq_abi_version() != ABI_VERSION:
         raise UqHipError('libuqhip.so ABI %d != binding ABI %d' % (lib.uq_abi_version(), ABI_VERSION))
     _lib = lib

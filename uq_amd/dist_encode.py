@@ -458,6 +458,10 @@ def main(argv=None):
     if getattr(args, 'gz', False) and not args.decode:
         print('ERROR: the sharded encoder writes a plain .uQ only; --gz is for the single-GPU encoder (python -m uq_amd.uq)')
         return 1
+    if getattr(args, 'qc', False):
+        print('ERROR: --qc is for the single-GPU tool (python -m uq_amd.uq); the tables of a sharded file are the sum of its shards\' '
+              '(uq_qc_accumulate), which this tool does not compute yet')
+        return 1
     if getattr(args, 'verify', False) or getattr(args, 'fingerprint', False):
         print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
               "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")

@@ -242,6 +242,130 @@ def fingerprint_json(fp):
     return json.dumps(d)
 
 
+# ------------------------------------------------------------------ the per-cycle tables uqqc1 (include/uqhip.h)
+QC_MAX_CYCLES, QC_NBASE, QC_NQUAL, QC_NGC = 1024, 6, 94, 101
+QC_SCALARS = ('reads', 'bases', 'qual_chars', 'qual_out_of_range', 'len_mismatch')
+
+
+def qc_words(ncycles):
+    """uq_qc_words: the number of u64 words of the object for ncycles exact cycles."""
+    n = int(ncycles)
+    if not 1 <= n <= QC_MAX_CYCLES: raise ValueError('qc: ncycles = %d is outside 1 .. %d' % (n, QC_MAX_CYCLES))
+    return int(load().uq_qc_words(n))
+
+
+def qc_new(ctx, ncycles=QC_MAX_CYCLES):
+    """A zeroed device uqqc1 object (int64[uq_qc_words]: the bit patterns of its u64 counters)."""
+    t = ctx.torch
+    d = t.empty(qc_words(ncycles), dtype=t.int64, device=ctx.device)
+    call('uq_qc_init', ctx.h, _p(d), int(ncycles))
+    return d
+
+
+def qc_accumulate(ctx, d_qc, buf, line_start, first_read, nreads, ncycles=QC_MAX_CYCLES):
+    """Adds the records [first_read, first_read + nreads) of buf into d_qc (queued, nothing read back)."""
+    if d_qc.numel() != qc_words(ncycles): raise ValueError('qc: the object holds %d words, ncycles = %d needs %d' % (d_qc.numel(), ncycles, qc_words(ncycles)))
+    call('uq_qc_accumulate', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), int(ncycles), _p(d_qc))
+
+
+def qc_fetch(ctx, d_qc):
+    """The device object as a flat uint64 array (synchronises)."""
+    return ctx.to_numpy(d_qc).view(np.uint64).copy()
+
+
+def qc(ctx, buf, line_start=None, nreads=None, ncycles=QC_MAX_CYCLES):
+    """The uqqc1 object of a FASTQ text in HBM (uint8 tensor); without an index it is built here (census + uq_index_lines)."""
+    if line_start is None:
+        nlines = count_lines(ctx, buf) if buf.numel() else 0
+        if nlines % 4: raise ValueError('qc: %d lines are not whole FASTQ records' % nlines)
+        nreads = nlines // 4
+        if nreads: line_start = index_lines(ctx, buf, nlines)
+    d = qc_new(ctx, ncycles)
+    if nreads: qc_accumulate(ctx, d, buf, line_start, 0, nreads, ncycles)
+    return qc_fetch(ctx, d)
+
+
+def qc_host(data, ncycles=QC_MAX_CYCLES, line_start=None, first_read=0, nreads=None):
+    """uq_qc_host: the same object on the CPU, sequentially, over host bytes (needs no GPU)."""
+    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    ls = np.ascontiguousarray(host_line_starts(a) if line_start is None else line_start, dtype=np.uint64)
+    if nreads is None:
+        if (len(ls) - 1) % 4: raise ValueError('qc: %d lines are not whole FASTQ records' % (len(ls) - 1))
+        nreads = (len(ls) - 1) // 4 - first_read
+    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('qc: records beyond the index')
+    out = np.zeros(qc_words(ncycles), dtype=np.uint64)
+    call('uq_qc_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(ncycles),
+         C.c_void_p(out.ctypes.data))
+    return out
+
+
+def qc_cycles(flat):
+    """The number of exact cycles of a flat uqqc1 array, from its length."""
+    c, r = divmod(len(flat) - 8 - QC_NQUAL - QC_NGC, QC_NBASE + QC_NQUAL + 1)
+    if r or not 1 <= c - 1 <= QC_MAX_CYCLES: raise ValueError('qc: %d words are no uqqc1 object' % len(flat))
+    return c - 1
+
+
+def qc_fields(flat):
+    """A flat uqqc1 array as a dict of its parts: the scalars as integers, the tables as uint64 views of `flat`."""
+    flat = np.asarray(flat, dtype=np.uint64)
+    c = qc_cycles(flat)
+    d = {k: int(flat[i]) for i, k in enumerate(QC_SCALARS)}
+    o = 8
+    for name, rows, cols in (('base_by_cycle', c + 1, QC_NBASE), ('qual_by_cycle', c + 1, QC_NQUAL), ('length_hist', c + 1, 0),
+                             ('mean_qual_hist', QC_NQUAL, 0), ('gc_hist', QC_NGC, 0)):
+        n = rows * max(cols, 1)
+        d[name] = flat[o:o + n].reshape(rows, cols) if cols else flat[o:o + n]
+        o += n
+    return d
+
+
+def qc_json(flat):
+    """The one line --qc prints.  Plain integers throughout.  The per-cycle tables and length_hist are cut after their last non-zero exact
+    cycle and qual_by_cycle's rows after the highest Phred value in use; the tail row (positions and lengths >= cycles) stands under
+    "beyond".  qc_from_json gives the flat array back exactly."""
+    import json
+    f = qc_fields(flat)
+    c = qc_cycles(flat)
+    base, qual, length = f['base_by_cycle'], f['qual_by_cycle'], f['length_hist']
+
+    def used(rows):
+        nz = np.flatnonzero(rows.reshape(len(rows), -1).any(axis=1))
+        return int(nz[-1]) + 1 if len(nz) else 0
+
+    nq = used(qual.T)
+    d = {'format': 'uqqc1', 'cycles': c}
+    for k in QC_SCALARS: d[k] = f[k]
+    d['base_classes'] = 'ACGTN*'
+    d['base_by_cycle'] = base[:used(base[:c])].tolist()
+    d['qual_by_cycle'] = qual[:used(qual[:c]), :nq].tolist()
+    d['length_hist'] = length[:used(length[:c])].tolist()
+    d['beyond'] = {'base': base[c].tolist(), 'qual': qual[c, :nq].tolist(), 'length': int(length[c])}
+    d['mean_qual_hist'] = f['mean_qual_hist'].tolist()
+    d['gc_hist'] = f['gc_hist'].tolist()
+    return json.dumps(d)
+
+
+def qc_from_json(line):
+    """The flat uqqc1 array of a line qc_json wrote."""
+    import json
+    d = json.loads(line)
+    if d.get('format') != 'uqqc1': raise ValueError('qc: not a uqqc1 line')
+    c = int(d['cycles'])
+    flat = np.zeros(qc_words(c), dtype=np.uint64)
+    f = qc_fields(flat)
+    for i, k in enumerate(QC_SCALARS): flat[i] = int(d[k])
+    for i, row in enumerate(d['base_by_cycle']): f['base_by_cycle'][i, :len(row)] = row
+    for i, row in enumerate(d['qual_by_cycle']): f['qual_by_cycle'][i, :len(row)] = row
+    f['length_hist'][:len(d['length_hist'])] = d['length_hist']
+    f['base_by_cycle'][c, :] = d['beyond']['base']
+    f['qual_by_cycle'][c, :len(d['beyond']['qual'])] = d['beyond']['qual']
+    f['length_hist'][c] = int(d['beyond']['length'])
+    f['mean_qual_hist'][:] = d['mean_qual_hist']
+    f['gc_hist'][:] = d['gc_hist']
+    return flat
+
+
 # ------------------------------------------------------------------ quality binning (include/uqhip.h, DESIGN.md section 21)
 def _lut_arg(lut):
     a = np.ascontiguousarray(np.frombuffer(bytes(lut), dtype=np.uint8))

@@ -87,6 +87,12 @@ def build_parser():
     p.add_argument('--fingerprint', action='store_true', default=False,
                    help='print the record fingerprint (uqfp1, DESIGN.md section 19: not cryptographic) of the input FASTQ as one JSON line and '
                         'write no container; with --decode: of the decoded text, and write no text (extension)')
+    p.add_argument('--qc', action='store_true', default=False,
+                   help='print the per-cycle base and quality tables, the read-length, mean-quality and GC histograms (uqqc1, DESIGN.md section 24) of '
+                        'the input FASTQ as one JSON line and write no container; with --bin-qual: of the binned text; with --decode: of the decoded '
+                        'text, and write no text (extension)')
+    p.add_argument('--qc-cycles', type=int, default=None, metavar='N',
+                   help='with --qc: the number of exact cycles, 1 .. 1024 (the default); positions from N on are counted together under "beyond" (extension)')
     from . import binqual
     p.add_argument('--bin-qual', action='store', default=None, metavar='SPEC', help=binqual.HELP)
     return p
@@ -127,6 +133,15 @@ def validate_args(args):
         if getattr(args, 'bgzf', False): error('ERROR: --fingerprint writes no text, so there is nothing for --bgzf to compress')
         if getattr(args, 'gz', False) or args.peek or args.test or args.output:
             error('ERROR: --fingerprint only reads: it does not go with --gz, --peek, --test or -o')
+    if getattr(args, 'qc_cycles', None) is not None:
+        if not getattr(args, 'qc', False): error('ERROR: --qc-cycles sets the number of exact cycles of --qc: use it together with --qc')
+        if not 1 <= args.qc_cycles <= 1024: error('ERROR: --qc-cycles is 1 .. 1024')
+    if getattr(args, 'qc', False):
+        if getattr(args, 'bgzf', False): error('ERROR: --qc writes no text, so there is nothing for --bgzf to compress')
+        if getattr(args, 'verify', False): error('ERROR: --qc writes no container, so there is nothing for --verify to read back')
+        if getattr(args, 'fingerprint', False): error('ERROR: --qc and --fingerprint each print their own line: run them one after the other')
+        if getattr(args, 'gz', False) or args.peek or args.test or args.output:
+            error('ERROR: --qc only reads: it does not go with --gz, --peek, --test or -o')
     if getattr(args, 'bin_qual', None) is not None:
         if args.decode: error('ERROR: --bin-qual changes the qualities an encode stores: the text --decode writes is what the container holds')
         bin_qual_table(args.bin_qual)
@@ -873,6 +888,21 @@ class Session:
         if show: print(self.ops.fingerprint_json(fp), file=self.out)
         return fp
 
+    # ------------------------------------------------------------------ the per-cycle tables
+    def qc_input(self):
+        """--qc: the input FASTQ goes to HBM as for --fingerprint (with --bin-qual it is binned there first); one kernel, one JSON line, no container."""
+        self.index_only = True
+        self.load(self.args.input)
+        qc = self.ops.qc(self.ctx, self.d_buf, self.d_ls, self.total, ncycles=self.args.qc_cycles or self.ops.QC_MAX_CYCLES)
+        print(self.ops.qc_json(qc), file=self.out)
+        return qc
+
+    def qc_decoded(self):
+        """--decode --qc: the tables of the text --decode would write (the text stays in HBM)."""
+        qc = self.ops.qc(self.ctx, self.decode_to_device(), ncycles=self.args.qc_cycles or self.ops.QC_MAX_CYCLES)
+        print(self.ops.qc_json(qc), file=self.out)
+        return qc
+
     VERIFY_DECODE_ERRORS = (UqError, RuntimeError, ValueError, IndexError, KeyError, OverflowError, OSError, EOFError)
 
     def verify(self):
@@ -1191,9 +1221,12 @@ def main(argv=None):
         ok = True
         if args.decode:
             if getattr(args, 'fingerprint', False): s.fingerprint_decoded()
+            elif getattr(args, 'qc', False): s.qc_decoded()
             else: s.decode()
         elif getattr(args, 'fingerprint', False):
             s.fingerprint_input()
+        elif getattr(args, 'qc', False):
+            s.qc_input()
         else:
             ok = s.encode()
         if os.environ.get('UQ_TIMING'):
