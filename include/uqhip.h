@@ -185,6 +185,38 @@ int uq_requantise_qualities(uq_ctx* ctx, uint8_t* d_buf, const uint64_t* d_line_
 int uq_requantise_qualities_host(uint8_t* h_buf, const uint64_t* h_line_start,
                                  uint64_t first_read, uint64_t nreads, const uint8_t* h_lut, uint64_t* h_changed);
 
+/* ---- paired-end input (`--mate2`, `--interleaved`; an extension: the reference reads one stream).  A paired container
+ * is the plain encode of the interleaved text: R1 record, its R2 record, the next R1 record, and so on.
+ * uq_interleave_records: d_ls_a / d_ls_b are the record indexes of d_a / d_b as uq_index_lines writes them.  With A(r) = the bytes
+ * [ls_a[4r], ls_a[4r + 4]) of d_a and B(r) likewise, writes A(first_pair) B(first_pair) A(first_pair + 1) B(first_pair + 1) ... for npairs
+ * pairs to d_out, from byte 0 on: with base = ls_a[4 first_pair] + ls_b[4 first_pair], A(r) lands at ls_a[4r] + ls_b[4r] - base and B(r) at
+ * ls_a[4r + 4] + ls_b[4r] - base.  The size, (ls_a[4 (first_pair + npairs)] - ls_a[4 first_pair]) + the same of b, is read back first:
+ * out_capacity below it is an error before anything is launched on the buffers.  Nothing outside [0, size) of d_out is written; npairs == 0
+ * is a no-op.  Any buffer alignment (the stores are 16-byte vectors at aligned addresses, single bytes at the output's two ends); lines
+ * shorter than 2^32 bytes; offsets are 64-bit everywhere; queued on the context's stream.  d_out must not overlap d_a or d_b.
+ * uq_mate_check: pair i, i < npairs, compares the QNAME line (line 1) of record first_a + i step_a of d_a with that of record
+ * first_b + i step_b of d_b -- two files: (0, 1) and (0, 1); one interleaved buffer: the same buffer and index twice, (0, 2) and (1, 2).
+ *   The id of a QNAME line, without its '\n', is its bytes up to but excluding the first ' ' or '\t'; the whole line if there is none.
+ *   If the id of a ends in "/1" and the id of b ends in "/2", those two bytes are dropped from both (the other way round is not dropped).
+ *   The pair matches when the two ids are then equal byte for byte.
+ * uq_mate_report (device, 8-byte aligned): pairs = the pairs counted; mismatches = the pairs that do not match; first_mismatch = the lowest
+ * pair_index_base + i that does not match (an atomic MIN: uq_mate_report_init sets it to UINT64_MAX and the counts to 0); slash_pairs = the
+ * pairs whose "/1" and "/2" were dropped.  Calls and shards add.  The kernel reads only the QNAME lines and their line starts and writes only
+ * the report; queued on the context's stream, nothing read back.
+ * uq_interleave_records_host, uq_mate_check_host: the same, sequentially, on host memory (need no GPU; the report is ADDED to). */
+typedef struct uq_mate_report { uint64_t pairs, mismatches, first_mismatch, slash_pairs; } uq_mate_report;
+int uq_interleave_records(uq_ctx* ctx, const uint8_t* d_a, const uint64_t* d_ls_a, const uint8_t* d_b, const uint64_t* d_ls_b,
+                          uint64_t first_pair, uint64_t npairs, uint8_t* d_out, uint64_t out_capacity);
+int uq_interleave_records_host(const uint8_t* h_a, const uint64_t* h_ls_a, const uint8_t* h_b, const uint64_t* h_ls_b,
+                               uint64_t first_pair, uint64_t npairs, uint8_t* h_out, uint64_t out_capacity);
+int uq_mate_report_init(uq_ctx* ctx, uq_mate_report* d_report);
+int uq_mate_check(uq_ctx* ctx, const uint8_t* d_a, const uint64_t* d_ls_a, uint64_t first_a, uint64_t step_a,
+                  const uint8_t* d_b, const uint64_t* d_ls_b, uint64_t first_b, uint64_t step_b,
+                  uint64_t npairs, uint64_t pair_index_base, uq_mate_report* d_report);
+int uq_mate_check_host(const uint8_t* h_a, const uint64_t* h_ls_a, uint64_t first_a, uint64_t step_a,
+                       const uint8_t* h_b, const uint64_t* h_ls_b, uint64_t first_b, uint64_t step_b,
+                       uint64_t npairs, uint64_t pair_index_base, uq_mate_report* h_report);
+
 /* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

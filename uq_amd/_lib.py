@@ -97,6 +97,10 @@ class Fingerprint(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ('reads', 'bases', 'plus_text', 'qname', 'dna', 'qual', 'pairs', 'records', 'ordered')]
 
 
+class MateReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('pairs', 'mismatches', 'first_mismatch', 'slash_pairs')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -144,6 +148,11 @@ SIGNATURES = {
     'uq_qc_host': [_vp, _vp, _u64, _u64, _u32, _vp],
     'uq_requantise_qualities': [_vp, _vp, _vp, _u64, _u64, _vp, _vp],
     'uq_requantise_qualities_host': [_vp, _vp, _u64, _u64, _vp, _P(_u64)],
+    'uq_interleave_records': [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64],
+    'uq_interleave_records_host': [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _u64],
+    'uq_mate_report_init': [_vp, _vp],
+    'uq_mate_check': [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _vp],
+    'uq_mate_check_host': [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _P(MateReport)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

@@ -462,6 +462,13 @@ def main(argv=None):
         print('ERROR: --qc is for the single-GPU tool (python -m uq_amd.uq); the tables of a sharded file are the sum of its shards\' '
               '(uq_qc_accumulate), which this tool does not compute yet')
         return 1
+    for flag, given in (('--mate2', getattr(args, 'mate2', None) is not None), ('--interleaved', getattr(args, 'interleaved', False)),
+                        ('--split-mates', getattr(args, 'split_mates', None) is not None)):
+        if given:
+            # like the checks around it: before any device or process-group set-up, so every rank stops alike and no collective is entered
+            print('ERROR: %s is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder and decoder do not keep the two mates of a '
+                  'pair on one rank yet' % flag)
+            return 1
     if getattr(args, 'verify', False) or getattr(args, 'fingerprint', False):
         print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
               "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")

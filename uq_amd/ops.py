@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -398,6 +398,87 @@ def requantise_qualities_host(data, lut, line_start=None, first_read=0, nreads=N
     call('uq_requantise_qualities_host', C.c_void_p(out.ctypes.data if out.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
          C.c_void_p(a.ctypes.data), C.byref(changed))
     return out, changed.value
+
+
+# ------------------------------------------------------------------ paired-end input (include/uqhip.h)
+MATE_REPORT_FIELDS = tuple(k for k, _ in MateReport._fields_)
+
+
+def interleaved_size(ctx, ls_a, ls_b, first_pair, npairs):
+    """The bytes uq_interleave_records writes for these pairs (four record starts brought down)."""
+    if npairs == 0: return 0
+    ends = [int(ctx.to_numpy(ls[4 * k:4 * k + 1], np.uint64)[0]) for ls in (ls_a, ls_b) for k in (first_pair, first_pair + npairs)]
+    return (ends[1] - ends[0]) + (ends[3] - ends[2])
+
+
+def interleave_records(ctx, buf_a, ls_a, buf_b, ls_b, first_pair, npairs, out=None, out_capacity=None):
+    """Records first_pair .. first_pair + npairs of buf_a and buf_b, alternating, from byte 0 of `out` on (queued; a new uint8 tensor of
+    exactly the size when `out` is None).  out_capacity: what the library is told `out` holds (its numel by default)."""
+    if out is None:
+        out = ctx.empty(interleaved_size(ctx, ls_a, ls_b, first_pair, npairs))
+    call('uq_interleave_records', ctx.h, _p(buf_a), _p(ls_a), _p(buf_b), _p(ls_b), int(first_pair), int(npairs), _p(out),
+         int(out.numel() if out_capacity is None else out_capacity))
+    return out
+
+
+def _host_text(data):
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+
+
+def interleave_records_host(a, b, ls_a=None, ls_b=None, first_pair=0, npairs=None):
+    """uq_interleave_records_host: the same on the CPU over host bytes (needs no GPU).  Returns a new uint8 array."""
+    a, b = _host_text(a), _host_text(b)
+    ls_a = np.ascontiguousarray(host_line_starts(a) if ls_a is None else ls_a, dtype=np.uint64)
+    ls_b = np.ascontiguousarray(host_line_starts(b) if ls_b is None else ls_b, dtype=np.uint64)
+    if npairs is None:
+        if (len(ls_a) - 1) % 4 or len(ls_a) != len(ls_b): raise ValueError('interleave: the two texts are not the same number of whole FASTQ records')
+        npairs = (len(ls_a) - 1) // 4 - first_pair
+    if first_pair < 0 or npairs < 0 or 4 * (first_pair + npairs) + 1 > min(len(ls_a), len(ls_b)): raise ValueError('interleave: records beyond the index')
+    size = 0 if npairs == 0 else int(ls_a[4 * (first_pair + npairs)] - ls_a[4 * first_pair]) + int(ls_b[4 * (first_pair + npairs)] - ls_b[4 * first_pair])
+    out = np.empty(size, dtype=np.uint8)
+    call('uq_interleave_records_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls_a.ctypes.data), C.c_void_p(b.ctypes.data if b.size else 0),
+         C.c_void_p(ls_b.ctypes.data), int(first_pair), int(npairs), C.c_void_p(out.ctypes.data if out.size else 0), size)
+    return out
+
+
+def mate_report_new(ctx):
+    """A device uq_mate_report (int64[4]) with its counts at 0 and first_mismatch at UINT64_MAX."""
+    t = ctx.torch
+    d = t.empty(len(MATE_REPORT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_mate_report_init', ctx.h, _p(d))
+    return d
+
+
+def mate_check(ctx, d_report, buf_a, ls_a, first_a, step_a, buf_b, ls_b, first_b, step_b, npairs, pair_index_base=0):
+    """Adds the pairs (record first_a + i step_a of buf_a, record first_b + i step_b of buf_b), i < npairs, into d_report (queued)."""
+    call('uq_mate_check', ctx.h, _p(buf_a), _p(ls_a), int(first_a), int(step_a), _p(buf_b), _p(ls_b), int(first_b), int(step_b), int(npairs),
+         int(pair_index_base), _p(d_report))
+
+
+def mate_report_fetch(ctx, d_report):
+    """The device report as a dict of Python integers (synchronises); first_mismatch is None when every pair matched."""
+    d = dict(zip(MATE_REPORT_FIELDS, (int(v) for v in ctx.to_numpy(d_report).view(np.uint64))))
+    if d['first_mismatch'] == UQ_NONE: d['first_mismatch'] = None
+    return d
+
+
+def mate_check_host(a, b, first_a=0, step_a=1, first_b=0, step_b=1, npairs=None, pair_index_base=0, ls_a=None, ls_b=None, report=None):
+    """uq_mate_check_host: the same on the CPU over host bytes (needs no GPU); `report`: a dict of an earlier call to add to."""
+    a, b = _host_text(a), _host_text(b)
+    ls_a = np.ascontiguousarray(host_line_starts(a) if ls_a is None else ls_a, dtype=np.uint64)
+    ls_b = np.ascontiguousarray(host_line_starts(b) if ls_b is None else ls_b, dtype=np.uint64)
+    if npairs is None: npairs = min(((len(ls_a) - 1) // 4 - first_a + step_a - 1) // step_a, ((len(ls_b) - 1) // 4 - first_b + step_b - 1) // step_b)
+    if npairs < 0 or first_a < 0 or first_b < 0 or step_a < 0 or step_b < 0: raise ValueError('mate check: negative argument')
+    if npairs and (4 * (first_a + (npairs - 1) * step_a) + 5 > len(ls_a) or 4 * (first_b + (npairs - 1) * step_b) + 5 > len(ls_b)):
+        raise ValueError('mate check: records beyond the index')
+    r = MateReport(0, 0, UQ_NONE, 0)
+    if report is not None:
+        r = MateReport(report['pairs'], report['mismatches'], UQ_NONE if report['first_mismatch'] is None else report['first_mismatch'], report['slash_pairs'])
+    call('uq_mate_check_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls_a.ctypes.data), int(first_a), int(step_a),
+         C.c_void_p(b.ctypes.data if b.size else 0), C.c_void_p(ls_b.ctypes.data), int(first_b), int(step_b), int(npairs), int(pair_index_base), C.byref(r))
+    d = {k: int(getattr(r, k)) for k in MATE_REPORT_FIELDS}
+    if d['first_mismatch'] == UQ_NONE: d['first_mismatch'] = None
+    return d
 
 
 # ------------------------------------------------------------------ pack

@@ -95,6 +95,17 @@ def build_parser():
                    help='with --qc: the number of exact cycles, 1 .. 1024 (the default); positions from N on are counted together under "beyond" (extension)')
     from . import binqual
     p.add_argument('--bin-qual', action='store', default=None, metavar='SPEC', help=binqual.HELP)
+    p.add_argument('--mate2', action='store', default=None, metavar='R2.fastq',
+                   help='paired-end input: -i is R1, this is R2 (plain, BGZF or other gzip, each by its content).  The read counts must be equal and '
+                        'read r of R2 must be the mate of read r of R1 (same QNAME up to the first space or tab, /1 with /2 allowed); the two '
+                        'files are interleaved on the GPU (R1 record, its R2 record, ...) and the container is the plain encode of that '
+                        'text, with a "paired" key in config.json (DESIGN.md section 25) (extension)')
+    p.add_argument('--interleaved', action='store_true', default=False,
+                   help='paired-end input in one file that already alternates R1 and R2: the mates are checked on the GPU and config.json '
+                        'gets the "paired" key (extension)')
+    p.add_argument('--split-mates', nargs=2, default=None, metavar=('OUT1', 'OUT2'),
+                   help='with --decode of a paired container: write mate 1 (the even records) to OUT1 and mate 2 (the odd records) to OUT2 '
+                        'instead of the interleaved text to stdout; with --bgzf both BGZF-compressed (extension)')
     return p
 
 
@@ -145,7 +156,20 @@ def validate_args(args):
     if getattr(args, 'bin_qual', None) is not None:
         if args.decode: error('ERROR: --bin-qual changes the qualities an encode stores: the text --decode writes is what the container holds')
         bin_qual_table(args.bin_qual)
+    mate2, interleaved, split = getattr(args, 'mate2', None), getattr(args, 'interleaved', False), getattr(args, 'split_mates', None)
+    if mate2 is not None and interleaved:
+        error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
+    if mate2 is not None or interleaved:
+        flag = '--mate2' if mate2 is not None else '--interleaved'
+        if args.decode: error('ERROR: %s describes the FASTQ an encode reads: it does not go with --decode (a paired container says so itself; see --split-mates)' % flag)
+        if isinstance(args.sort, str) and args.sort.lower() in ('dna', 'qual', 'qname'):
+            error('ERROR: --sort %s tears mates apart: a paired container keeps R1 and R2 of a pair next to each other, so %s does not go with --sort' % (args.sort, flag))
+    if split is not None:
+        if not args.decode: error('ERROR: --split-mates writes the two mates of a paired container: use it together with --decode')
+        if getattr(args, 'fingerprint', False) or getattr(args, 'qc', False): error('ERROR: --fingerprint and --qc write no text, so there is nothing for --split-mates to split')
+        if os.path.abspath(split[0]) == os.path.abspath(split[1]): error('ERROR: --split-mates needs two different output files')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
+    if mate2 is not None and not os.path.isfile(mate2): error('ERROR: Sorry, the --mate2 path you have specified is not a file!')
     return args
 
 
@@ -230,14 +254,19 @@ class Session:
         self.load_device(d_buf, census=census.get('c'))
 
     def load_gzip(self, path):
-        """gzip input (an extension: the reference reads plain text only), recognised by its magic bytes.  BGZF (every member carries its
+        """gzip input (an extension: the reference reads plain text only), recognised by its magic bytes: gzip_to_device, then load_device."""
+        d_buf = self.gzip_to_device(path)
+        self.path, self._host = None, None             # the file holds compressed bytes: the host copy (`host`) comes from d_buf
+        self.load_device(d_buf)
+
+    def gzip_to_device(self, path):
+        """A gzip file's text as a device buffer.  BGZF (every member carries its
         compressed size): the compressed file goes to HBM, the member headers are walked on the host, every member inflates on the device
         into its slice of one buffer (uq_inflate_members).  Any other gzip goes to HBM compressed and inflates there in parallel chunks
-        (uq_gzip_stream_*, GZIP_STREAM_CHUNK bytes each); --host-inflate: on the host (zlib), streamed to HBM.  Then load_device."""
+        (uq_gzip_stream_*, GZIP_STREAM_CHUNK bytes each); --host-inflate: on the host (zlib), streamed to HBM."""
         ops, ctx = self.ops, self.ctx
         kind, members, total, err = ops.gzip_scan(np.memmap(path, dtype=np.uint8, mode='r'))
         if kind == ops.GZIP_MALFORMED: error('ERROR: %s is not a readable gzip file: %s' % (path, err[0]))
-        self.path, self._host = None, None             # the file holds compressed bytes: the host copy (`host`) comes from d_buf
         if kind == ops.GZIP_BGZF:
             self.gzip_path = 'BGZF, %d members inflated on the device' % len(members)
             d_comp = self.io.file_to_device(path)
@@ -265,7 +294,68 @@ class Session:
             self.gzip_stream_info = info
             self.gzip_path = 'gzip, %d chunks inflated on the device' % info['chunks']
         if d_buf.numel() == 0: error('ERROR: empty input')
-        self.load_device(d_buf)
+        return d_buf
+
+    def text_to_device(self, path):
+        """One input file of either kind -> its FASTQ text in HBM, without load_device (the paired loader: the single-input path keeps its
+        chunked census behind the PCIe copies, `load`)."""
+        if os.path.getsize(path) == 0: error('ERROR: empty input')
+        return self.gzip_to_device(path) if self.ops.is_gzip(path) else self.io.file_to_device(path)
+
+    # ------------------------------------------------------------------ paired-end input (DESIGN.md section 25)
+    pairing = None             # --mate2 / --interleaved: config.json's "paired" value
+
+    def load_input(self):
+        """The input of an encode (or of --fingerprint / --qc) in HBM: one file, two mates interleaved on the device, or one interleaved file."""
+        args = self.args
+        if getattr(args, 'mate2', None) is not None: return self.load_pairs(args.input, args.mate2)
+        self.load(args.input)
+        if getattr(args, 'interleaved', False): self.check_interleaved()
+
+    def indexed(self, d_buf, what):
+        """(reads, record index) of a text in HBM."""
+        nlines = self.ops.count_lines(self.ctx, d_buf)
+        if nlines % 4 != 0: error('ERROR: %s contains %d rows, which is not divisible by 4!' % (what, nlines))
+        if nlines == 0: error('ERROR: empty input')
+        return nlines // 4, self.ops.index_lines(self.ctx, d_buf, nlines)
+
+    def require_mates(self, d_a, ls_a, first_a, step_a, d_b, ls_b, first_b, step_b, npairs):
+        """uq_mate_check over the pairs; a pair that does not match is a refusal, with its two QNAME lines fetched from HBM."""
+        ops, ctx = self.ops, self.ctx
+        d_rep = ops.mate_report_new(ctx)
+        ops.mate_check(ctx, d_rep, d_a, ls_a, first_a, step_a, d_b, ls_b, first_b, step_b, npairs)
+        rep = ops.mate_report_fetch(ctx, d_rep)
+        if rep['mismatches']:
+            k = rep['first_mismatch']
+
+            def qname_line(d, ls, r):
+                lo, hi = (int(v) for v in ctx.to_numpy(ls[4 * r:4 * r + 2], np.uint64))
+                return ctx.to_numpy(d[lo:hi - 1]).tobytes().decode('latin-1')
+            error('ERROR: pair %d: %s and %s are not mates (%d of %d pairs differ)' % (
+                k, qname_line(d_a, ls_a, first_a + k * step_a), qname_line(d_b, ls_b, first_b + k * step_b), rep['mismatches'], rep['pairs']))
+        self.pairing = {'layout': 'interleaved', 'pairs': rep['pairs'], 'slash_pairs': rep['slash_pairs']}
+
+    def load_pairs(self, path1, path2):
+        """-i R1 --mate2 R2: both files to HBM by the loaders of their kinds, lines counted and indexed, equal read counts, uq_mate_check,
+        uq_interleave_records into a new buffer (the inputs are freed), then load_device as for a file with those bytes."""
+        ops, ctx = self.ops, self.ctx
+        d_1 = self.text_to_device(path1)
+        d_2 = self.text_to_device(path2)
+        n1, ls_1 = self.indexed(d_1, 'R1 (%s)' % path1)
+        n2, ls_2 = self.indexed(d_2, 'R2 (%s)' % path2)
+        if n1 != n2: error('ERROR: R1 holds %d reads, R2 holds %d' % (n1, n2))
+        self.require_mates(d_1, ls_1, 0, 1, d_2, ls_2, 0, 1, n1)
+        d_out = ctx.empty(d_1.numel() + d_2.numel())
+        ops.interleave_records(ctx, d_1, ls_1, d_2, ls_2, 0, n1, out=d_out)
+        ctx.sync()
+        del d_1, d_2, ls_1, ls_2
+        self.path, self._host = None, None             # no file holds the interleaved bytes: the host copy (`host`) comes from d_buf
+        self.load_device(d_out)
+
+    def check_interleaved(self):
+        """--interleaved, behind `load`: an even read count, and record 2i + 1 the mate of record 2i (one buffer, nothing copied)."""
+        if self.total % 2: error('ERROR: --interleaved: the input holds %d reads, an odd number: R1 and R2 do not alternate' % self.total)
+        self.require_mates(self.d_buf, self.d_ls, 0, 2, self.d_buf, self.d_ls, 1, 2, self.total // 2)
 
     def load_device(self, d_buf, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
@@ -479,6 +569,7 @@ class Session:
             'QNAME_prefix': prefix, 'QNAME_suffix': suffix, 'QNAME_separators': separators, 'QNAME_columns': columns,
         }
         if binning is not None: self.config['quality_binning'] = binning
+        if self.pairing is not None: self.config['paired'] = dict(self.pairing)
 
     def report(self, prefix, suffix, separators):
         """The analysis printout of uq.py:459-545 (condensed: same facts, fewer bar charts)."""
@@ -868,7 +959,7 @@ class Session:
         args = self.args
         if args.output is None: args.output = args.input + ('.uQ.gz' if getattr(args, 'gz', False) else '.uQ')
         self.say('Warming up...')
-        self.load(args.input)
+        self.load_input()
         self.encode_loaded()
         return self.verify() if getattr(args, 'verify', False) else True
 
@@ -877,7 +968,7 @@ class Session:
         """--fingerprint: the input FASTQ (plain, BGZF or other gzip) goes to HBM as for an encode, only the record index is built; one JSON
         line, no container."""
         self.index_only = True
-        self.load(self.args.input)
+        self.load_input()
         fp = self.ops.fingerprint(self.ctx, self.d_buf, self.d_ls, self.total)
         print(self.ops.fingerprint_json(fp), file=self.out)
         return fp
@@ -892,7 +983,7 @@ class Session:
     def qc_input(self):
         """--qc: the input FASTQ goes to HBM as for --fingerprint (with --bin-qual it is binned there first); one kernel, one JSON line, no container."""
         self.index_only = True
-        self.load(self.args.input)
+        self.load_input()
         qc = self.ops.qc(self.ctx, self.d_buf, self.d_ls, self.total, ncycles=self.args.qc_cycles or self.ops.QC_MAX_CYCLES)
         print(self.ops.qc_json(qc), file=self.out)
         return qc
@@ -931,6 +1022,7 @@ class Session:
                 args.output, want['reads'], 'as a multiset, resorted by --sort ' + args.sort if resorted else 'in the same order',
                 key + ' fingerprint equal', hx(got['records']))
             if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
+            if self.pairing is not None: line += '; %d pairs, mates interleaved' % self.pairing['pairs']
             if getattr(args, 'bin_qual', None) is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
                 line += '; qualities binned by --bin-qual %s, %d characters changed' % (args.bin_qual, self.binned_changed_in_file())
             show(line)
@@ -1044,18 +1136,26 @@ class Session:
         """BGZF containers: how many of the file's members this session has inflated on the device so far (None for other sources)."""
         return getattr(self.source, 'inflated_members', None)
 
-    def load_tables(self, members, config, rows=None):
+    def load_tables(self, members, config, rows=None, mate=None):
         """uq.py:943-973 on the device: the DNA / QUAL tables as (tensor, reads, row bytes) and the QNAME columns, in
         stored read order; `rows` = (lo, hi) restricts all of them to that range of reads (keys are sliced, the
-        tables they index are loaded whole)."""
+        tables they index are loaded whole).  `mate` = 0 / 1 (--split-mates): the even / the odd reads only -- a raw table is
+        gathered with a stride-2 index (uq_gather_rows), a key or a raw column is sliced with that stride before it is used."""
         ops, ctx = self.ops, self.ctx
         pat = config['pattern'] or ['0.1', '0.1']
 
+        def half(d):                                                                               # a key or a column: every second element
+            return d if mate is None else d[mate::2].contiguous()
+
         def table(name, pattern):
-            if name + '.raw' in members: return self.load_from_tar(members, name + '.raw', pattern, rows)
+            if name + '.raw' in members:
+                t, nrows, cols = self.load_from_tar(members, name + '.raw', pattern, rows)
+                if mate is None: return (t, nrows, cols)
+                d_idx = ctx.torch.arange(mate, nrows, 2, dtype=ctx.torch.int64, device=ctx.device)
+                return (ops.gather_rows(ctx, t, nrows, cols, d_idx), d_idx.numel(), cols)
             if name in members and name + '.key' in members:
                 t, nrows, cols = self.load_from_tar(members, name, pattern)
-                d_key = self.load_from_tar(members, name + '.key', rows=rows)
+                d_key = half(self.load_from_tar(members, name + '.key', rows=rows))
                 self.check_index(d_key, nrows, name + '.key')
                 return (ops.gather_rows(ctx, t, nrows, cols, d_key), d_key.numel(), cols)          # uq.py:953, 957
             error('ERROR: No ' + name + ' data was found in this uQ file?!')
@@ -1065,14 +1165,14 @@ class Session:
         ncols = len(config['QNAME_columns'])
         u8 = ctx.torch.uint8
         if 'QNAME.key' in members:
-            d_key = self.load_from_tar(members, 'QNAME.key', rows=rows)
+            d_key = half(self.load_from_tar(members, 'QNAME.key', rows=rows))
             d_cols = []
             for i in range(ncols):                                                                # uq.py:973, numeric order (Q6)
                 c = self.load_from_tar(members, 'QNAME_%d' % (i + 1))
                 if i == 0: self.check_index(d_key, c.numel(), 'QNAME.key')
                 d_cols.append(ops.gather_rows(ctx, c.view(u8), c.numel(), c.element_size(), d_key).view(c.dtype))
         else:
-            d_cols = [self.load_from_tar(members, 'QNAME_%d.raw' % (i + 1), rows=rows) for i in range(ncols)]
+            d_cols = [half(self.load_from_tar(members, 'QNAME_%d.raw' % (i + 1), rows=rows)) for i in range(ncols)]
         for i, c in enumerate(config['QNAME_columns']):                                           # uq.py:1016 `column['map'][row[i]]`
             if c['format'] == 'mapping': self.check_index(d_cols[i], len(c['map']), 'QNAME column %d' % (i + 1))
         if len({DNA[1], QUAL[1]} | {c.numel() for c in d_cols}) != 1:
@@ -1110,12 +1210,16 @@ class Session:
 
     def decode_tables(self):
         """The container of args.input opened and checked, its tables in HBM: (config, DNA, QUAL, QNAME columns)."""
+        members, config = self.decode_open()
+        return (config,) + tuple(self.load_tables(members, config))
+
+    def decode_open(self):
+        """The container of args.input opened and checked: (members, config)."""
         from . import container
         # a compressed container is verified whole (every member's length and CRC-32) before the first byte of text leaves
         self.source, self.tar_path = container.open_source(self, self.args.input), self.args.input
         if self.source.kind == container.BGZF: self.source.verify_all()
-        members, config = self.open_container()
-        return (config,) + tuple(self.load_tables(members, config))
+        return self.open_container()
 
     def host_text_records(self, config, DNA, QUAL, d_cols):
         """The text of a file whose QNAME lines the device kernels cannot write (device_text_possible), record by record: sequence and quality
@@ -1138,10 +1242,31 @@ class Session:
         return self.ctx.bytes_to_device(b''.join(self.host_text_records(config, DNA, QUAL, d_cols)))
 
     def decode(self, out=None):
-        ctx = self.ctx
         out = out or sys.stdout
         config, DNA, QUAL, d_cols = self.decode_tables()
-        w = out.buffer if hasattr(out, 'buffer') else out
+        self.write_text(config, DNA, QUAL, d_cols, out.buffer if hasattr(out, 'buffer') else out)
+
+    def decode_split(self, out1, out2):
+        """--decode --split-mates OUT1 OUT2: the even reads of a paired container to OUT1, the odd ones to OUT2.  The two halves of every
+        table are made on the device (load_tables with `mate`); each goes through the unchanged text path into its own file."""
+        members, config = self.decode_open()
+        if 'paired' not in config:
+            error('ERROR: --split-mates needs a paired container and the config.json of %s has no "paired" key: if its reads alternate R1 and R2, '
+                  'decode it and encode the text again with --interleaved' % self.args.input)
+        if config['reads'] % 2: error('ERROR: this uQ file says it is paired and holds %d reads, an odd number' % config['reads'])
+        for mate, path in enumerate((out1, out2)):
+            DNA, QUAL, d_cols = self.load_tables(members, config, mate=mate)
+            tmp = path + '.tmp%d' % os.getpid()
+            try:
+                with open(tmp, 'wb') as w: self.write_text(config, DNA, QUAL, d_cols, w)
+                os.replace(tmp, path)
+            finally:
+                if os.path.exists(tmp): os.remove(tmp)
+            del DNA, QUAL, d_cols
+
+    def write_text(self, config, DNA, QUAL, d_cols, w):
+        """The FASTQ text of these tables into the binary stream w (--bgzf: BGZF-compressed)."""
+        ctx = self.ctx
         bgzf = getattr(self.args, 'bgzf', False)
         if self.device_text_possible(config):
             # the text streams out through the pinned buffers (--bgzf: deflated on the device first)
@@ -1222,6 +1347,7 @@ def main(argv=None):
         if args.decode:
             if getattr(args, 'fingerprint', False): s.fingerprint_decoded()
             elif getattr(args, 'qc', False): s.qc_decoded()
+            elif getattr(args, 'split_mates', None): s.decode_split(*args.split_mates)
             else: s.decode()
         elif getattr(args, 'fingerprint', False):
             s.fingerprint_input()
