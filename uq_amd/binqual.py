@@ -14,7 +14,7 @@ bases: the encoder then still takes N out of the alphabet, but under a NEW quali
 container does not give its reads back (`--verify` says so), and the way out, --notricks, costs 3 bits per base instead of 2 (+50 % on the
 DNA table).
 """
-from .uq import UqError
+from .errors import UqError
 
 OFFSET = 33
 QMAX = 93

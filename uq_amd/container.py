@@ -17,6 +17,8 @@ import tarfile
 
 import numpy as np
 
+from .errors import error as _error
+
 BGZF_BLOCK = 65280
 BLOCKSIZE, RECORDSIZE = tarfile.BLOCKSIZE, tarfile.RECORDSIZE
 
@@ -24,9 +26,6 @@ PLAIN, BGZF, GZIP = 'plain', 'bgzf', 'gzip'
 OTHER_MAGIC = ((b'BZh', 'bzip2'), (b'\xfd7zXZ\x00', 'xz'), (b'\x28\xb5\x2f\xfd', 'zstd'))
 
 
-def _error(message):
-    from .uq import UqError
-    raise UqError(message)
 
 
 def sniff(path):
@@ -189,7 +188,7 @@ def open_source(session, path):
             session.say('Warning: %s has no BGZF EOF member; it may be truncated' % path)
         return BgzfSource(comp, members, total, device_inflater(ops, ctx, lambda lo, n: session.io.file_to_device(path, lo, n), members, path), name=path)
     del comp
-    if getattr(session.args, 'host_inflate', False):
+    if session.args.host_inflate:
         import zlib
         try:
             return BufferSource(ctx, session.io.gzip_to_device(path))

@@ -32,7 +32,8 @@ import time
 import numpy as np
 
 from . import dist as uqdist
-from .uq import Session, UqError, build_parser, error, npy_header, pattern_header, validate_args
+from .errors import UqError, error
+from .uq import Session, build_parser, npy_header, pattern_header, validate_args, whole_records
 
 # pattern id -> (column-major?, rows flipped?, columns flipped?)   (csrc/pattern.hip)
 PATTERN_FLAGS = {'0.1': (0, 0, 0), '0.2': (1, 0, 0), '1.1': (1, 0, 1), '1.2': (0, 0, 1),
@@ -48,6 +49,7 @@ class ShardedSession(Session):
         self.be = uqdist.HipRows(self.ctx)
         self.group = group
         self.dist, self.rank, self.world = uqdist._world()
+        self._binned_total = None  # --bin-qual: the file's count of changed quality characters, summed over the ranks once
         if self.rank != 0: args.quiet = True
 
     # ------------------------------------------------------------------ errors are agreed on
@@ -97,10 +99,7 @@ class ShardedSession(Session):
             owner = max(r for r in range(self.world) if per_rank[r] > 0)
             per_rank[owner] -= 1
             if owner == self.rank: mine -= 1
-        total_lines = sum(per_rank)
-        if total_lines % 4 != 0:
-            error('ERROR: The FASTQ file provided contains' + str(total_lines) + 'rows, which is not divisible by 4!')
-        if total_lines == 0: error('ERROR: empty input')
+        whole_records(sum(per_rank))
         first_line = sum(per_rank[:self.rank])                     # file-wide number of my first line start
         j0 = (-first_line) % 4                                     # my first record starts at my j0-th line start
         n = max(0, -(-(mine - j0) // 4))
@@ -124,8 +123,8 @@ class ShardedSession(Session):
             self.load_device(chunk[start:end])
             if self.total != n: error('ERROR: rank %d counted %d reads in a shard of %d' % (self.rank, self.total, n))
         else:
+            self._reset_load_state()
             self.d_buf, self.d_ls = chunk[:0], t.zeros(1, dtype=t.int64, device=ctx.device)
-            self._spec, self._fq, self._guess_shared = None, None, False
             self.d_stats = ops.stats_new(ctx)
         if self.fused_qname_enabled() and not self._guess_shared:
             # a rank without reads, or whose head gave no guess of its own, still takes part in the broadcast (its analyse_qname says "not usable")
@@ -168,7 +167,7 @@ class ShardedSession(Session):
 
     def binned_changed_in_file(self):
         """--bin-qual: every rank binned its own shard at the head of load_device; the file's count is the sum (collective)."""
-        if getattr(self, '_binned_total', None) is None:
+        if self._binned_total is None:
             self._binned_total = int(self.shard.reduce([int(self.binned_changed)], 'sum')[0])
         return self._binned_total
 
@@ -177,7 +176,7 @@ class ShardedSession(Session):
         res = None
         if self.fused_qname_enabled():           # collective: every rank enters, a rank whose own pass did not hold says so inside
             self.qname_path = 'fused'
-            fq, self._fq = getattr(self, '_fq', None), None
+            fq, self._fq = self._fq, None
             res = qname_device.analyse_fused_sharded(self.ctx, fq, self.total, self.shard, usable=fq is not None or self.total == 0)
         if res is None:
             self.qname_path = 'device'
@@ -334,45 +333,39 @@ class ShardedSession(Session):
     # ------------------------------------------------------------------ container
     def write_container(self, path):
         """uq.py:897-913 with every rank writing its pieces: the tar layout follows from the member sizes alone."""
-        args = self.args
-        cfg = dict(self.config)
-        cfg['sort'] = args.sort if isinstance(args.sort, str) else [None]
-        cfg['raw'] = sorted(args.raw, key=str) if args.raw else [None]
-        cfg['pattern'] = list(args.pattern) if args.pattern else None
-        self.config = cfg
-        blob = json.dumps(cfg, indent=4, sort_keys=True).encode()
-
-        def order(name):
-            base = name.split('.')[0]
-            if base.startswith('QNAME_'): return (3, int(base[6:]), name)
-            return ({'DNA': 0, 'QUAL': 1, 'QNAME': 2}.get(base, 4), 0, name)
-
-        names = sorted(self.members, key=order)
-        layout, pos = [], 0                         # (name, header bytes, tar header offset, payload offset, size)
+        blob, names = self.closing_config()
+        layout, pos = [], 0                        # (name, header bytes, tar header offset, payload offset, size)
         for name, header, size in [('config.json', blob, 0)] + [(k, self.members[k][0], self.members[k][1]) for k in names]:
             layout.append((name, header, pos, pos + tarfile.BLOCKSIZE + len(header), len(header) + size))
             pos += tarfile.BLOCKSIZE + len(header) + size
             pos += -pos % tarfile.BLOCKSIZE
         end = pos + 2 * tarfile.BLOCKSIZE
         end += -end % tarfile.RECORDSIZE
-        tmp = path + '.part'
         mtime = self.shard.reduce([int(time.time())], 'min')[0]
-        def create():
-            if self.rank != 0: return None
-            f = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-            os.ftruncate(f, end)                                   # sparse zeros: tar padding and end blocks are already there
+
+        def headers(f):                                            # (the file is sparse zeros: tar padding and end blocks are already there)
             for name, header, hpos, _, size in layout:
                 ti = tarfile.TarInfo(name); ti.size = size; ti.mtime = mtime
                 os.pwrite(f, ti.tobuf(tarfile.DEFAULT_FORMAT, tarfile.ENCODING, 'surrogateescape') + header, hpos)
+        self.write_together(path, end, [(ppos + off, piece) for name, _, _, ppos, _ in layout[1:] for off, piece in self.members[name][2]], headers)
+
+    def write_together(self, path, size, pieces, head=None):
+        """One file of `size` bytes written by all ranks: rank 0 creates path.part at its final size and writes head(fd) into it, every
+        rank puts its pieces [(file offset, device bytes)] in place, rank 0 renames.  What fails on one rank is every rank's UqError."""
+        tmp = path + '.part'
+
+        def create():
+            if self.rank != 0: return None
+            f = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            os.ftruncate(f, size)
+            if head is not None: head(f)
             return f
         fd = self.guarded(create, 'creating ' + tmp)               # also the barrier: the file exists at its final size
 
         def put():
             f = fd if self.rank == 0 else os.open(tmp, os.O_WRONLY)
             try:
-                for name, _, _, ppos, _ in layout[1:]:
-                    for off, piece in self.members[name][2]:
-                        self.io.device_to_fd(piece, f, ppos + off)
+                for off, piece in pieces: self.io.device_to_fd(piece, f, off)
             finally:
                 os.close(f)
         try:
@@ -380,9 +373,7 @@ class ShardedSession(Session):
         except UqError:
             if self.rank == 0 and os.path.exists(tmp): os.remove(tmp)
             raise
-        if self.rank == 0:
-            os.replace(tmp, path)
-
+        if self.rank == 0: os.replace(tmp, path)
 
     # ------------------------------------------------------------------ decode
     def decode_sharded(self, out_path):
@@ -401,7 +392,7 @@ class ShardedSession(Session):
             DNA, QUAL, d_cols = self.load_tables(members, config, rows=(lo, hi))
             if hi > lo: text = self.decode_text(config, DNA, QUAL, d_cols)
             else: text = self.ctx.torch.empty(0, dtype=self.ctx.torch.uint8, device=self.ctx.device)
-            if getattr(self.args, 'bgzf', False):
+            if self.args.bgzf:
                 # every rank deflates its own text into whole members; the last one appends the EOF member
                 text = self.ops.bgzf_compress(self.ctx, text, eof=self.rank == self.world - 1, level=self.bgzf_level)
             return text, lo, n
@@ -413,28 +404,7 @@ class ShardedSession(Session):
         shard = uqdist.Shard(self.be, lo, n, self.group)
         sizes = shard.gather_ints(int(text.numel()))
         offset, total = sum(sizes[:self.rank]), sum(sizes)
-        tmp = out_path + '.part'
-
-        def create():
-            if self.rank != 0: return None
-            f = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-            os.ftruncate(f, total)
-            return f
-        fd = self.guarded(create, 'creating ' + tmp)               # also the barrier: the file exists at its final size
-
-        def put():
-            f = fd if self.rank == 0 else os.open(tmp, os.O_WRONLY)
-            try:
-                if text.numel(): self.io.device_to_fd(text, f, offset)
-            finally:
-                os.close(f)
-        try:
-            self.guarded(put, 'writing ' + tmp)                    # also the barrier: all pieces are in place
-        except UqError:
-            if self.rank == 0 and os.path.exists(tmp): os.remove(tmp)
-            raise
-        if self.rank == 0:
-            os.replace(tmp, out_path)
+        self.write_together(out_path, total, [(offset, text)] if text.numel() else [])
 
     def member_rows(self, members, name, pattern='0.1'):
         """Rows of a 2-D member / elements of a 1-D one, from its .npy header."""
@@ -455,21 +425,20 @@ def main(argv=None):
             # before any device or process-group set-up: every rank reads the same two bytes and stops alike
             print('ERROR: the sharded encoder reads plain FASTQ only; encode gzip input on one GPU (python -m uq_amd.uq) or decompress it first')
             return 1
-    if getattr(args, 'gz', False) and not args.decode:
+    if args.gz and not args.decode:
         print('ERROR: the sharded encoder writes a plain .uQ only; --gz is for the single-GPU encoder (python -m uq_amd.uq)')
         return 1
-    if getattr(args, 'qc', False):
+    if args.qc:
         print('ERROR: --qc is for the single-GPU tool (python -m uq_amd.uq); the tables of a sharded file are the sum of its shards\' '
               '(uq_qc_accumulate), which this tool does not compute yet')
         return 1
-    for flag, given in (('--mate2', getattr(args, 'mate2', None) is not None), ('--interleaved', getattr(args, 'interleaved', False)),
-                        ('--split-mates', getattr(args, 'split_mates', None) is not None)):
+    for flag, given in (('--mate2', args.mate2 is not None), ('--interleaved', args.interleaved), ('--split-mates', args.split_mates is not None)):
         if given:
             # like the checks around it: before any device or process-group set-up, so every rank stops alike and no collective is entered
             print('ERROR: %s is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder and decoder do not keep the two mates of a '
                   'pair on one rank yet' % flag)
             return 1
-    if getattr(args, 'verify', False) or getattr(args, 'fingerprint', False):
+    if args.verify or args.fingerprint:
         print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
               "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")
         return 1
@@ -514,7 +483,7 @@ def main(argv=None):
     finally:
         if os.environ.get('UQ_TIMING') and rank == 0:
             print(json.dumps({'uq_timing': 'dist_encode', 'world': world, 'work_s': round(time.perf_counter() - t_ready, 3),
-                              'load': getattr(session, 'load_path', None), 'qname': getattr(session, 'qname_path', None)}),
+                              'load': session and session.load_path, 'qname': session and session.qname_path}),
                   file=sys.stderr, flush=True)
         dist.destroy_process_group()
     return code

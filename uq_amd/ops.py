@@ -202,13 +202,16 @@ def fingerprint_fetch(ctx, d_fp):
     return dict(zip(FINGERPRINT_FIELDS, (int(v) for v in ctx.to_numpy(d_fp).view(np.uint64))))
 
 
+def _indexed(ctx, buf, who):
+    """(record index, reads) of a FASTQ text in HBM whose caller brought no index: census + uq_index_lines (no reads: no index)."""
+    nlines = count_lines(ctx, buf) if buf.numel() else 0
+    if nlines % 4: raise ValueError('%s: %d lines are not whole FASTQ records' % (who, nlines))
+    return (index_lines(ctx, buf, nlines) if nlines else None), nlines // 4
+
+
 def fingerprint(ctx, buf, line_start=None, nreads=None):
     """The fingerprint of a FASTQ text in HBM (uint8 tensor); without an index it is built here (census + uq_index_lines)."""
-    if line_start is None:
-        nlines = count_lines(ctx, buf) if buf.numel() else 0
-        if nlines % 4: raise ValueError('fingerprint: %d lines are not whole FASTQ records' % nlines)
-        nreads = nlines // 4
-        if nreads: line_start = index_lines(ctx, buf, nlines)
+    if line_start is None: line_start, nreads = _indexed(ctx, buf, 'fingerprint')
     d = fingerprint_new(ctx)
     if nreads: fingerprint_accumulate(ctx, d, buf, line_start, 0, nreads)
     return fingerprint_fetch(ctx, d)
@@ -220,14 +223,26 @@ def host_line_starts(data):
     return np.concatenate(([0], np.flatnonzero(a == 10) + 1)).astype(np.uint64)
 
 
+def _host_indexed(data, line_start):
+    """A host twin's text and index as it passes them on: (contiguous uint8 array, contiguous uint64 line starts -- the caller's, or made here)."""
+    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    return a, np.ascontiguousarray(host_line_starts(a) if line_start is None else line_start, dtype=np.uint64)
+
+
+def _host_records(data, line_start, first_read, nreads, who):
+    """_host_indexed and the records [first_read, first_read + nreads) checked against the index (nreads None: all from first_read on, of
+    a text of whole records) -> (bytes, line starts, nreads)."""
+    a, ls = _host_indexed(data, line_start)
+    if nreads is None:
+        if (len(ls) - 1) % 4: raise ValueError('%s: %d lines are not whole FASTQ records' % (who, len(ls) - 1))
+        nreads = (len(ls) - 1) // 4 - first_read
+    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('%s: records beyond the index' % who)
+    return a, ls, nreads
+
+
 def fingerprint_host(data, line_start=None, first_read=0, nreads=None, index_base=0):
     """uq_fingerprint_host: the same sums on the CPU, sequentially, over host bytes (needs no GPU)."""
-    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
-    ls = np.ascontiguousarray(host_line_starts(a) if line_start is None else line_start, dtype=np.uint64)
-    if nreads is None:
-        if (len(ls) - 1) % 4: raise ValueError('fingerprint: %d lines are not whole FASTQ records' % (len(ls) - 1))
-        nreads = (len(ls) - 1) // 4 - first_read
-    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('fingerprint: records beyond the index')
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'fingerprint')
     fp = Fingerprint()
     call('uq_fingerprint_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
          int(index_base), C.byref(fp))
@@ -275,11 +290,7 @@ def qc_fetch(ctx, d_qc):
 
 def qc(ctx, buf, line_start=None, nreads=None, ncycles=QC_MAX_CYCLES):
     """The uqqc1 object of a FASTQ text in HBM (uint8 tensor); without an index it is built here (census + uq_index_lines)."""
-    if line_start is None:
-        nlines = count_lines(ctx, buf) if buf.numel() else 0
-        if nlines % 4: raise ValueError('qc: %d lines are not whole FASTQ records' % nlines)
-        nreads = nlines // 4
-        if nreads: line_start = index_lines(ctx, buf, nlines)
+    if line_start is None: line_start, nreads = _indexed(ctx, buf, 'qc')
     d = qc_new(ctx, ncycles)
     if nreads: qc_accumulate(ctx, d, buf, line_start, 0, nreads, ncycles)
     return qc_fetch(ctx, d)
@@ -287,12 +298,7 @@ def qc(ctx, buf, line_start=None, nreads=None, ncycles=QC_MAX_CYCLES):
 
 def qc_host(data, ncycles=QC_MAX_CYCLES, line_start=None, first_read=0, nreads=None):
     """uq_qc_host: the same object on the CPU, sequentially, over host bytes (needs no GPU)."""
-    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
-    ls = np.ascontiguousarray(host_line_starts(a) if line_start is None else line_start, dtype=np.uint64)
-    if nreads is None:
-        if (len(ls) - 1) % 4: raise ValueError('qc: %d lines are not whole FASTQ records' % (len(ls) - 1))
-        nreads = (len(ls) - 1) // 4 - first_read
-    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('qc: records beyond the index')
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'qc')
     out = np.zeros(qc_words(ncycles), dtype=np.uint64)
     call('uq_qc_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(ncycles),
          C.c_void_p(out.ctypes.data))
@@ -388,12 +394,8 @@ def requantise_qualities(ctx, buf, line_start, first_read, nreads, lut, d_change
 
 def requantise_qualities_host(data, lut, line_start=None, first_read=0, nreads=None):
     """uq_requantise_qualities_host: the same on the CPU over host bytes (needs no GPU).  Returns (a new uint8 array, bytes changed)."""
-    out = np.array(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8, order='C')
-    ls = np.ascontiguousarray(host_line_starts(out) if line_start is None else line_start, dtype=np.uint64)
-    if nreads is None:
-        if (len(ls) - 1) % 4: raise ValueError('requantise: %d lines are not whole FASTQ records' % (len(ls) - 1))
-        nreads = (len(ls) - 1) // 4 - first_read
-    if first_read < 0 or nreads < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('requantise: records beyond the index')
+    out, ls, nreads = _host_records(data, line_start, first_read, nreads, 'requantise')
+    out = np.array(out, dtype=np.uint8, order='C')      # (a copy: the caller's text stays as it is)
     a, changed = _lut_arg(lut), C.c_uint64(0)
     call('uq_requantise_qualities_host', C.c_void_p(out.ctypes.data if out.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
          C.c_void_p(a.ctypes.data), C.byref(changed))
@@ -421,19 +423,14 @@ def interleave_records(ctx, buf_a, ls_a, buf_b, ls_b, first_pair, npairs, out=No
     return out
 
 
-def _host_text(data):
-    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
-
-
 def interleave_records_host(a, b, ls_a=None, ls_b=None, first_pair=0, npairs=None):
     """uq_interleave_records_host: the same on the CPU over host bytes (needs no GPU).  Returns a new uint8 array."""
-    a, b = _host_text(a), _host_text(b)
-    ls_a = np.ascontiguousarray(host_line_starts(a) if ls_a is None else ls_a, dtype=np.uint64)
-    ls_b = np.ascontiguousarray(host_line_starts(b) if ls_b is None else ls_b, dtype=np.uint64)
     if npairs is None:
+        (a, ls_a), (b, ls_b) = _host_indexed(a, ls_a), _host_indexed(b, ls_b)
         if (len(ls_a) - 1) % 4 or len(ls_a) != len(ls_b): raise ValueError('interleave: the two texts are not the same number of whole FASTQ records')
         npairs = (len(ls_a) - 1) // 4 - first_pair
-    if first_pair < 0 or npairs < 0 or 4 * (first_pair + npairs) + 1 > min(len(ls_a), len(ls_b)): raise ValueError('interleave: records beyond the index')
+    a, ls_a, _ = _host_records(a, ls_a, first_pair, npairs, 'interleave')
+    b, ls_b, _ = _host_records(b, ls_b, first_pair, npairs, 'interleave')
     size = 0 if npairs == 0 else int(ls_a[4 * (first_pair + npairs)] - ls_a[4 * first_pair]) + int(ls_b[4 * (first_pair + npairs)] - ls_b[4 * first_pair])
     out = np.empty(size, dtype=np.uint8)
     call('uq_interleave_records_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls_a.ctypes.data), C.c_void_p(b.ctypes.data if b.size else 0),
@@ -464,9 +461,7 @@ def mate_report_fetch(ctx, d_report):
 
 def mate_check_host(a, b, first_a=0, step_a=1, first_b=0, step_b=1, npairs=None, pair_index_base=0, ls_a=None, ls_b=None, report=None):
     """uq_mate_check_host: the same on the CPU over host bytes (needs no GPU); `report`: a dict of an earlier call to add to."""
-    a, b = _host_text(a), _host_text(b)
-    ls_a = np.ascontiguousarray(host_line_starts(a) if ls_a is None else ls_a, dtype=np.uint64)
-    ls_b = np.ascontiguousarray(host_line_starts(b) if ls_b is None else ls_b, dtype=np.uint64)
+    (a, ls_a), (b, ls_b) = _host_indexed(a, ls_a), _host_indexed(b, ls_b)      # (the pairs its strides reach: the arithmetic below is its own)
     if npairs is None: npairs = min(((len(ls_a) - 1) // 4 - first_a + step_a - 1) // step_a, ((len(ls_b) - 1) // 4 - first_b + step_b - 1) // step_b)
     if npairs < 0 or first_a < 0 or first_b < 0 or step_a < 0 or step_b < 0: raise ValueError('mate check: negative argument')
     if npairs and (4 * (first_a + (npairs - 1) * step_a) + 5 > len(ls_a) or 4 * (first_b + (npairs - 1) * step_b) + 5 > len(ls_b)):

@@ -29,18 +29,22 @@ import time
 
 import numpy as np
 
+from .errors import UqError, error
+
 # compressed bytes per chunk of a gzip file that is not BGZF, inflated on the device
 GZIP_STREAM_CHUNK = 1 << 18
 
 PATTERNS = ['0.1', '1.1', '2.1', '3.1', '0.2', '1.2', '2.2', '3.2']
 
 
-class UqError(Exception):
-    """The reference prints and exit()s (uq.py:48-50); the library form raises, main() prints."""
-
-
-def error(message):
-    raise UqError(message)
+def whole_records(nlines, what=None):
+    """The reads of a text of `nlines` lines, or the refusal of a line count that is not whole records (uq.py:85-87, its missing spaces
+    included); `what` names the text where a session holds more than one."""
+    if nlines % 4 != 0:
+        if what is None: error('ERROR: The FASTQ file provided contains' + str(nlines) + 'rows, which is not divisible by 4!')
+        error('ERROR: %s contains %d rows, which is not divisible by 4!' % (what, nlines))
+    if nlines == 0: error('ERROR: empty input')
+    return nlines // 4
 
 
 def build_parser():
@@ -122,41 +126,40 @@ def validate_args(args):
         args.raw = set(args.raw)
         if 'none' in args.raw:
             args.raw.add(None); args.raw.discard('none')
-    if getattr(args, 'bgzf', False) and not args.decode: error('ERROR: --bgzf compresses decoded FASTQ: use it together with --decode')
-    if getattr(args, 'gz', False):
+    if args.bgzf and not args.decode: error('ERROR: --bgzf compresses decoded FASTQ: use it together with --decode')
+    if args.gz:
         if args.decode: error('ERROR: --gz compresses the container the encoder writes: --decode recognises a compressed container by itself')
         if args.peek: error('ERROR: --gz compresses the container the encoder writes: --peek writes none')
-    if getattr(args, 'device_compressor', False):
+    if args.device_compressor:
         if args.compressor: error('ERROR: --device-compressor and --compressor are two ways to size the same candidates: give one of them')
         if not args.test: error('ERROR: --device-compressor sizes the candidates of --test: use it together with --test')
-    if getattr(args, 'bgzf_level', None) is not None:
+    if args.bgzf_level is not None:
         if args.bgzf_level not in (1, 2): error('ERROR: --bgzf-level is 1 or 2')
-        if not ((getattr(args, 'bgzf', False) and args.decode) or getattr(args, 'gz', False) or
-                (getattr(args, 'device_compressor', False) and args.test)):
+        if not ((args.bgzf and args.decode) or args.gz or (args.device_compressor and args.test)):
             error('ERROR: --bgzf-level sets the level of the GPU deflate compressor: use it together with --decode --bgzf, --gz or '
                   '--test --device-compressor')
-    if getattr(args, 'verify', False):
+    if args.verify:
         if args.decode: error('ERROR: --verify checks the container an encode writes: it does not go with --decode')
         if args.peek: error('ERROR: --verify reads back the container the encoder writes: --peek writes none')
         if args.test: error('ERROR: --verify does not go with --test: encode with the parameters --test found, then verify that file')
-        if getattr(args, 'fingerprint', False): error('ERROR: --fingerprint writes no container, so there is nothing for --verify to read back')
-    if getattr(args, 'fingerprint', False):
-        if getattr(args, 'bgzf', False): error('ERROR: --fingerprint writes no text, so there is nothing for --bgzf to compress')
-        if getattr(args, 'gz', False) or args.peek or args.test or args.output:
+        if args.fingerprint: error('ERROR: --fingerprint writes no container, so there is nothing for --verify to read back')
+    if args.fingerprint:
+        if args.bgzf: error('ERROR: --fingerprint writes no text, so there is nothing for --bgzf to compress')
+        if args.gz or args.peek or args.test or args.output:
             error('ERROR: --fingerprint only reads: it does not go with --gz, --peek, --test or -o')
-    if getattr(args, 'qc_cycles', None) is not None:
-        if not getattr(args, 'qc', False): error('ERROR: --qc-cycles sets the number of exact cycles of --qc: use it together with --qc')
+    if args.qc_cycles is not None:
+        if not args.qc: error('ERROR: --qc-cycles sets the number of exact cycles of --qc: use it together with --qc')
         if not 1 <= args.qc_cycles <= 1024: error('ERROR: --qc-cycles is 1 .. 1024')
-    if getattr(args, 'qc', False):
-        if getattr(args, 'bgzf', False): error('ERROR: --qc writes no text, so there is nothing for --bgzf to compress')
-        if getattr(args, 'verify', False): error('ERROR: --qc writes no container, so there is nothing for --verify to read back')
-        if getattr(args, 'fingerprint', False): error('ERROR: --qc and --fingerprint each print their own line: run them one after the other')
-        if getattr(args, 'gz', False) or args.peek or args.test or args.output:
+    if args.qc:
+        if args.bgzf: error('ERROR: --qc writes no text, so there is nothing for --bgzf to compress')
+        if args.verify: error('ERROR: --qc writes no container, so there is nothing for --verify to read back')
+        if args.fingerprint: error('ERROR: --qc and --fingerprint each print their own line: run them one after the other')
+        if args.gz or args.peek or args.test or args.output:
             error('ERROR: --qc only reads: it does not go with --gz, --peek, --test or -o')
-    if getattr(args, 'bin_qual', None) is not None:
+    if args.bin_qual is not None:
         if args.decode: error('ERROR: --bin-qual changes the qualities an encode stores: the text --decode writes is what the container holds')
         bin_qual_table(args.bin_qual)
-    mate2, interleaved, split = getattr(args, 'mate2', None), getattr(args, 'interleaved', False), getattr(args, 'split_mates', None)
+    mate2, interleaved, split = args.mate2, args.interleaved, args.split_mates
     if mate2 is not None and interleaved:
         error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
     if mate2 is not None or interleaved:
@@ -166,7 +169,7 @@ def validate_args(args):
             error('ERROR: --sort %s tears mates apart: a paired container keeps R1 and R2 of a pair next to each other, so %s does not go with --sort' % (args.sort, flag))
     if split is not None:
         if not args.decode: error('ERROR: --split-mates writes the two mates of a paired container: use it together with --decode')
-        if getattr(args, 'fingerprint', False) or getattr(args, 'qc', False): error('ERROR: --fingerprint and --qc write no text, so there is nothing for --split-mates to split')
+        if args.fingerprint or args.qc: error('ERROR: --fingerprint and --qc write no text, so there is nothing for --split-mates to split')
         if os.path.abspath(split[0]) == os.path.abspath(split[1]): error('ERROR: --split-mates needs two different output files')
     if not os.path.isfile(args.input): error('ERROR: Sorry, the input path you have specified is not a file!')
     if mate2 is not None and not os.path.isfile(mate2): error('ERROR: Sorry, the --mate2 path you have specified is not a file!')
@@ -174,14 +177,9 @@ def validate_args(args):
 
 
 def bin_qual_table(spec):
-    """--bin-qual SPEC -> (the 256-byte table, the explicit form of the spec); a bad spec is this module's UqError (run as a script, this
-    module is `__main__` and uq_amd.binqual raises the class of `uq_amd.uq`)."""
+    """--bin-qual SPEC -> (the 256-byte table, the explicit form of the spec); a bad spec is a UqError."""
     from . import binqual
-    try:
-        return binqual.parse(spec), binqual.explicit(spec)
-    except Exception as e:
-        if type(e).__name__ != 'UqError': raise
-        error(str(e))
+    return binqual.parse(spec), binqual.explicit(spec)
 
 
 def npy_header(shape, fortran_order, dtype):
@@ -208,7 +206,7 @@ class Session:
         from .device import Context
         self.ops = ops
         self.args = args
-        self.ctx = ctx or Context(getattr(args, 'device', 0))
+        self.ctx = ctx or Context(args.device)
         from .hostio import Staging
         self.io = Staging(self.ctx)
         self.out = out
@@ -224,9 +222,36 @@ class Session:
         self.gz_layout = None      # --gz: name -> {'frame': (offset, bytes), 'data': (offset, bytes)} in the compressed file
         self.tar_path = None
         self.source = None         # decode: the container's byte source (uq_amd/container.py)
+        self.path = None           # the plain FASTQ file `load` read (None: no file holds the bytes of d_buf)
+        self._host = None          # host copy of the FASTQ bytes, made on first use (`host`)
+        self.side = None           # the second context the head guess runs on, made by the first queued load and kept
+        self.index_only = False    # --fingerprint / --qc: the load stops at the line count
+        self.pairing = None        # --mate2 / --interleaved: config.json's "paired" value
+        self.bin_qual_ranges = None    # --bin-qual: the explicit form of the spec
+        self.binned_changed = 0    # --bin-qual: quality characters this session's binning changed
+        self.d_buf = None          # the FASTQ text in HBM (uint8 device tensor)
+        self.total = 0             # reads in d_buf
+        self.d = None              # analyse: the decisions of analysis.decide_from_stats
+        self.hs = None             # analyse: the host copy of the statistics (ops.HostStats)
+        self.qname_arrays = []     # analyse: one array of values per QNAME column
+        self.load_path = None      # which pipeline load_device took
+        self.pack_path = None      # 'speculative' (the load's tables were kept) or 'plain'
+        self.qname_path = None     # 'fused', 'device', 'host-native' or 'host-python'
+        self.gzip_path = None      # gzip input: how it was inflated
+        self.gzip_stream_info = None   # gzip input that is not BGZF: what ops.gzip_stream_to_device reports
+        self._reset_load_state()
+
+    def _reset_load_state(self):
+        """What one load leaves for analyse and pack, back to empty: load_device does this first."""
+        self._d_ls = None          # the record index (`d_ls`), expanded on first use
+        self._spec = None          # (guessed uq_pack_params, dna, qual, bad) of a speculative pack, until _encode takes or drops it
+        self._fq = None            # the ops.FusedQname the pack kernel filled, until analyse_qname takes it
+        self._guess_shared = False  # the QNAME guess has been handed to share_qname_guess in this load
+        self.d_stats = None        # the statistics in HBM (device uq_stats)
+        self.load_path = None
 
     def say(self, *a):
-        if not getattr(self.args, 'quiet', False):
+        if not self.args.quiet:
             print(*a, file=self.out)
 
     def split_time(self):
@@ -276,7 +301,7 @@ class Session:
                 k, st = bad
                 error('ERROR: %s: gzip member %d (deflate data at byte %d): %s' % (path, k, int(members[k]['data_offset']),
                                                                                   ops.INFLATE_STATUS.get(st, 'status %d' % st)))
-        elif getattr(self.args, 'host_inflate', False):
+        elif self.args.host_inflate:
             self.gzip_path = 'gzip inflated on the host'
             import zlib
             try:
@@ -303,21 +328,17 @@ class Session:
         return self.gzip_to_device(path) if self.ops.is_gzip(path) else self.io.file_to_device(path)
 
     # ------------------------------------------------------------------ paired-end input
-    pairing = None             # --mate2 / --interleaved: config.json's "paired" value
-
     def load_input(self):
         """The input of an encode (or of --fingerprint / --qc) in HBM: one file, two mates interleaved on the device, or one interleaved file."""
         args = self.args
-        if getattr(args, 'mate2', None) is not None: return self.load_pairs(args.input, args.mate2)
+        if args.mate2 is not None: return self.load_pairs(args.input, args.mate2)
         self.load(args.input)
-        if getattr(args, 'interleaved', False): self.check_interleaved()
+        if args.interleaved: self.check_interleaved()
 
     def indexed(self, d_buf, what):
         """(reads, record index) of a text in HBM."""
         nlines = self.ops.count_lines(self.ctx, d_buf)
-        if nlines % 4 != 0: error('ERROR: %s contains %d rows, which is not divisible by 4!' % (what, nlines))
-        if nlines == 0: error('ERROR: empty input')
-        return nlines // 4, self.ops.index_lines(self.ctx, d_buf, nlines)
+        return whole_records(nlines, what), self.ops.index_lines(self.ctx, d_buf, nlines)
 
     def require_mates(self, d_a, ls_a, first_a, step_a, d_b, ls_b, first_b, step_b, npairs):
         """uq_mate_check over the pairs; a pair that does not match is a refusal, with its two QNAME lines fetched from HBM."""
@@ -359,92 +380,94 @@ class Session:
 
     def load_device(self, d_buf, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
-        all been queued -- load() queues them behind the PCIe copies).  The default is the step bench.py times, queued back
-        to back: the census's closing scan (the line count stays on the device) -> the QNAME layout guess from a sample of the reads ->
-        pack + pass-1 statistics + QNAME fields in ONE kernel, with decisions guessed from the head of the file (a second context's
-        stream works them out beside the census) and verified afterwards against the whole file's counts.  NO record index is written:
-        the kernels walk the census's newline lists; `d_ls` is expanded on first use by whatever still wants it (the exact QNAME kernels,
-        the plain packers, the N-trick's first occurrences).  The stream is read twice.  --multi-pass: census -> index -> statistics ->
-        pack as separate passes (three reads).  Same results whichever path."""
-        ops, ctx, args = self.ops, self.ctx, self.args
+        all been queued -- load() queues them behind the PCIe copies).  --bin-qual first; then the line count alone (--fingerprint, --qc),
+        or the queued step bench.py times, or -- where that does not hold for this file -- the same two reads with the record index,
+        or -- where that has no kernel either, and under --multi-pass -- the plain statistics pass.  Same results whichever path."""
+        self._reset_load_state()
         self.d_buf = d_buf
-        if not hasattr(self, '_host'): self.path, self._host = None, None
-        binned = self.bin_qualities(census) if getattr(args, 'bin_qual', None) is not None else None      # (line count, record index)
+        binned = self.bin_qualities(census) if self.args.bin_qual is not None else None      # (line count, record index)
         if binned is not None: census = None             # (its census has been closed; the step below runs its own: one more census per encode, with the flag only)
-        if getattr(self, 'index_only', False):           # --fingerprint: the line count and (on first use) the record index, no statistics, no pack
-            self._spec, self._fq, self._d_ls, self.load_path = None, None, None, 'index only'
-            if binned is not None: nlines, self._d_ls = binned
-            else: nlines = census.end() if census is not None else ops.count_lines(ctx, d_buf)
-            if nlines % 4 != 0:
-                error('ERROR: The FASTQ file provided contains' + str(nlines) + 'rows, which is not divisible by 4!')
-            if nlines == 0: error('ERROR: empty input')
-            self.total = nlines // 4
-            return
-        self._spec, self._fq, self._d_ls, self.load_path = None, None, None if binned is None else binned[1], 'multi-pass'
-        self._guess_shared = False
-        nbytes = int(d_buf.numel())
-        nlines, queued, guess, cap = None, None, None, 0
-        if not getattr(args, 'multi_pass', False) and nbytes:
-            if census is None:
-                ctx.sync()                               # (whoever made the buffer may still be writing it: the guess's stream does not wait for this one)
-                census = ops.ChunkedCensus(ctx, d_buf)
-                census.chunk(0, nbytes)
-            census.end_async()
-            if getattr(self, 'side', None) is None:
-                from .device import SideContext
-                self.side = SideContext(ctx)            # the guess's small census / index / statistics must not touch the queued census's state
-            g = ops.head_guess(self.side, d_buf, notricks=args.notricks, pad=args.pad, head_bytes=ops.HEAD_BYTES_SMALL, head_reads=ops.HEAD_READS_INDEXED)
-            if g is not None:
-                guess, rpb = g
-                cap = int(nbytes * rpb * 1.02) + 1024
-                guess.avg_record_bytes = int(1.0 / rpb)
-                fq = None
-                if self.fused_qname_enabled():
-                    fq = ops.FusedQname(ctx, cap)
-                    if self.owns_qname_guess(): ops.qname_guess_async(ctx, d_buf, None, fq)
-                    self.share_qname_guess(fq)
-                queued = ops.pack_stats_async(ctx, d_buf, None, cap, guess, fq=fq)
-                if queued is not None and fq is not None: ops.qname_fused_finish(ctx, fq)
-            nlines, ok = census.wait()
-            if not ok:                                   # a tile with more newlines than a list holds (lines of a few bytes): the bitmap form
-                nlines, queued = ops.count_lines(ctx, d_buf), None
-        elif census is not None:
-            nlines = census.end()
-        if nlines is None:
-            nlines = ops.count_lines(ctx, self.d_buf)
-        if nlines % 4 != 0:
-            error('ERROR: The FASTQ file provided contains' + str(nlines) + 'rows, which is not divisible by 4!')
-        if nlines == 0: error('ERROR: empty input')
-        self.total = nlines // 4
-        if queued is not None and self.total <= cap:
-            n = self.total
-            self._spec = (guess, queued[0][:n * guess.dna_bytes_per_row], queued[1][:n * guess.quality_bytes_per_row], queued[2])
-            self.d_stats = queued[3]
-            self.load_path = 'two reads (census; pack + statistics), queued, no record index'
-            self._fq = fq
-        elif not getattr(args, 'multi_pass', False):
-            # the queued form does not hold for this file (more reads than the head promised, a head without a whole record, an alphabet
-            # without a fused kernel): the same two reads through the plain calls, with the index
-            del queued
-            guess = ops.head_guess_indexed(ctx, self.d_buf, self.d_ls, self.total, args.notricks, args.pad)
-            fq = None
-            if guess is not None and self.fused_qname_enabled() and not self._guess_shared:
-                fq = ops.FusedQname(ctx, self.total)
-                if self.owns_qname_guess(): ops.qname_guess(ctx, self.d_buf, self.d_ls, self.total, fq)
-                self.share_qname_guess(fq)
-            res = ops.pack_stats(ctx, self.d_buf, self.d_ls, 0, self.total, guess, fq=fq) if guess is not None else None
-            if res is not None:
-                self._spec = (guess,) + res[:3]
-                self.d_stats = res[3]
-                self.load_path = 'two reads (census; pack + statistics)'
-                if fq is not None:
-                    ops.qname_fused_finish(ctx, fq)
-                    self._fq = fq
-        if self._spec is None:
-            self.d_stats = ops.stats_new(ctx)
-            ops.stats_accumulate(ctx, self.d_stats, self.d_buf, self.d_ls, 0, self.total)
+        if self.index_only: return self._load_index_only(census, binned)
+        if binned is not None: self._d_ls = binned[1]
+        self.load_path = 'multi-pass'
+        if self.args.multi_pass or not d_buf.numel():
+            self.total = whole_records(census.end() if census is not None else self.ops.count_lines(self.ctx, d_buf))
+        elif self._load_queued(census) is None:
+            self._load_indexed()
+        if self._spec is None: self._load_plain_stats()
 
-    binned_changed = 0         # --bin-qual: quality characters this session's binning changed
+    def _load_index_only(self, census, binned):
+        """--fingerprint, --qc: the line count and (on first use) the record index, no statistics, no pack."""
+        self.load_path = 'index only'
+        if binned is not None: nlines, self._d_ls = binned
+        else: nlines = census.end() if census is not None else self.ops.count_lines(self.ctx, self.d_buf)
+        self.total = whole_records(nlines)
+
+    def _load_queued(self, census):
+        """The default, the step bench.py times, queued back to back: the census's closing scan (the line count
+        stays on the device) -> the QNAME layout guess from a sample of the reads -> pack + pass-1 statistics + QNAME fields in ONE
+        kernel, with decisions guessed from the head of the file (a second context's stream works them out beside the census) and verified
+        afterwards against the whole file's counts.  NO record index is written: the kernels walk the census's newline lists; `d_ls` is
+        expanded on first use by whatever still wants it (the exact QNAME kernels, the plain packers, the N-trick's first occurrences).
+        The stream is read twice.  Sets `total`; returns None, with nothing kept, when the queued form does not hold for this file."""
+        ops, ctx, args, d_buf = self.ops, self.ctx, self.args, self.d_buf
+        nbytes = int(d_buf.numel())
+        if census is None:
+            ctx.sync()                                   # (whoever made the buffer may still be writing it: the guess's stream does not wait for this one)
+            census = ops.ChunkedCensus(ctx, d_buf)
+            census.chunk(0, nbytes)
+        census.end_async()
+        if self.side is None:
+            from .device import SideContext
+            self.side = SideContext(ctx)                # the guess's small census / index / statistics must not touch the queued census's state
+        g = ops.head_guess(self.side, d_buf, notricks=args.notricks, pad=args.pad, head_bytes=ops.HEAD_BYTES_SMALL, head_reads=ops.HEAD_READS_INDEXED)
+        queued, fq, cap = None, None, 0
+        if g is not None:
+            guess, rpb = g
+            cap = int(nbytes * rpb * 1.02) + 1024
+            guess.avg_record_bytes = int(1.0 / rpb)
+            if self.fused_qname_enabled():
+                fq = ops.FusedQname(ctx, cap)
+                if self.owns_qname_guess(): ops.qname_guess_async(ctx, d_buf, None, fq)
+                self.share_qname_guess(fq)
+            queued = ops.pack_stats_async(ctx, d_buf, None, cap, guess, fq=fq)
+            if queued is not None and fq is not None: ops.qname_fused_finish(ctx, fq)
+        nlines, ok = census.wait()
+        if not ok:                                       # a tile with more newlines than a list holds (lines of a few bytes): the bitmap form
+            nlines, queued = ops.count_lines(ctx, d_buf), None
+        n = self.total = whole_records(nlines)
+        if queued is None or n > cap: return None
+        self._spec = (guess, queued[0][:n * guess.dna_bytes_per_row], queued[1][:n * guess.quality_bytes_per_row], queued[2])
+        self.d_stats = queued[3]
+        self.load_path = 'two reads (census; pack + statistics), queued, no record index'
+        self._fq = fq
+        return self._spec
+
+    def _load_indexed(self):
+        """The queued form does not hold for this file (more reads than the head promised, a head without a whole record, a census list
+        overflow, an alphabet without a fused kernel): the same two reads through the plain calls, with the record index.  Leaves `_spec`
+        None when there is no fused kernel for this file either."""
+        ops, ctx, args = self.ops, self.ctx, self.args
+        guess = ops.head_guess_indexed(ctx, self.d_buf, self.d_ls, self.total, args.notricks, args.pad)
+        if guess is None: return
+        fq = None
+        if self.fused_qname_enabled() and not self._guess_shared:
+            fq = ops.FusedQname(ctx, self.total)
+            if self.owns_qname_guess(): ops.qname_guess(ctx, self.d_buf, self.d_ls, self.total, fq)
+            self.share_qname_guess(fq)
+        res = ops.pack_stats(ctx, self.d_buf, self.d_ls, 0, self.total, guess, fq=fq)
+        if res is None: return
+        self._spec = (guess,) + res[:3]
+        self.d_stats = res[3]
+        self.load_path = 'two reads (census; pack + statistics)'
+        if fq is not None:
+            ops.qname_fused_finish(ctx, fq)
+            self._fq = fq
+
+    def _load_plain_stats(self):
+        """--multi-pass, and whatever the speculative forms left: the statistics as a pass of their own over the record index."""
+        self.d_stats = self.ops.stats_new(self.ctx)
+        self.ops.stats_accumulate(self.ctx, self.d_stats, self.d_buf, self.d_ls, 0, self.total)
 
     def bin_qualities(self, census=None):
         """--bin-qual, at the head of load_device: the table of the spec applied to every quality line of self.d_buf, in place
@@ -468,7 +491,7 @@ class Session:
 
     # the fused QNAME pass's seams (the sharded session overrides the last two: rank 0's guess is every rank's)
     def fused_qname_enabled(self):
-        return not getattr(self.args, 'multi_pass', False) and not getattr(self.args, 'host_qname', False) and not getattr(self.args, 'exact_qname', False)
+        return not self.args.multi_pass and not self.args.host_qname and not self.args.exact_qname
 
     def owns_qname_guess(self):
         return True
@@ -480,7 +503,7 @@ class Session:
     @property
     def d_ls(self):
         """The record index (uint64 offset of every line start), expanded when somebody asks for it: the default encode never does."""
-        if getattr(self, '_d_ls', None) is None:
+        if self._d_ls is None:
             self._d_ls = self.ops.index_lines(self.ctx, self.d_buf, 4 * self.total)
         return self._d_ls
 
@@ -502,8 +525,7 @@ class Session:
         hs = self.ops.stats_fetch(self.ctx, self.d_stats)
         if hs.incomplete:                        # the speculative pass could not count everything: plain statistics pass
             self._spec = None
-            self.d_stats = self.ops.stats_new(self.ctx)
-            self.ops.stats_accumulate(self.ctx, self.d_stats, self.d_buf, self.d_ls, 0, self.total)
+            self._load_plain_stats()
             hs = self.ops.stats_fetch(self.ctx, self.d_stats)
         return hs
 
@@ -521,12 +543,12 @@ class Session:
         subset that path reproduces exactly, and with --host-qname -- sequentially on the host."""
         from . import qname, qname_device
         self.qname_path = 'fused'
-        fq, self._fq = getattr(self, '_fq', None), None
+        fq, self._fq = self._fq, None
         res = qname_device.analyse_fused(self.ctx, fq, self.total) if fq is not None else None
         del fq
         if res is None:
             self.qname_path = 'device'
-            res = None if getattr(self.args, 'host_qname', False) else qname_device.analyse_device(self.ctx, self.d_buf, self.d_ls, self.total)
+            res = None if self.args.host_qname else qname_device.analyse_device(self.ctx, self.d_buf, self.d_ls, self.total)
         if res is None:
             self.qname_path = 'host-native'
             h_ls = self.ctx.to_numpy(self.d_ls, np.uint64)
@@ -556,8 +578,8 @@ class Session:
         self.columns = columns
         self.qname_arrays = arrays
         binning = None
-        if getattr(args, 'bin_qual', None) is not None:
-            binning = {'spec': args.bin_qual, 'ranges': getattr(self, 'bin_qual_ranges', None) or bin_qual_table(args.bin_qual)[1],
+        if args.bin_qual is not None:
+            binning = {'spec': args.bin_qual, 'ranges': self.bin_qual_ranges or bin_qual_table(args.bin_qual)[1],
                        'changed': self.binned_changed_in_file()}
             self.say('Binned qualities (%s): %d of %d quality characters changed' % (args.bin_qual, binning['changed'], sum(d['qual_distribution'].values())))
         self.report(prefix, suffix, separators)
@@ -598,15 +620,13 @@ class Session:
         say('    - we will use', d['dna_bytes_per_row'], 'bytes per unique DNA sequence.\n')
         say('QUAL Analysis:')
         quals_all = sorted(d['qual_distribution'])
-        counts = getattr(getattr(self, 'hs', None), 'counts', None)
-        if counts is not None:                                                  # uq.py:520-526: the per-base breakdown
-            for b in bases_all:
-                say('  [Breakdown for "' + b + '"]')
-                row = counts[ord(b)]
-                for q in np.flatnonzero(row):
-                    pct = int(row[q]) / float(d['base_distribution'][b]) * 100
-                    say('     ', chr(q), '|' + ('#' * int(pct / 2)).ljust(50) + '|', ('%.3f' % pct).rjust(7) + '%', str(int(row[q])).rjust(12))
-                say('')
+        for b in bases_all:                                                     # uq.py:520-526: the per-base breakdown
+            say('  [Breakdown for "' + b + '"]')
+            row = self.hs.counts[ord(b)]
+            for q in np.flatnonzero(row):
+                pct = int(row[q]) / float(d['base_distribution'][b]) * 100
+                say('     ', chr(q), '|' + ('#' * int(pct / 2)).ljust(50) + '|', ('%.3f' % pct).rjust(7) + '%', str(int(row[q])).rjust(12))
+            say('')
         say('  [Total distribution]')
         say('    - the following values were seen as quality scores:', ' '.join(quals_all), '(' + str(len(quals_all)) + ' in total)')
         say('    - There distribution is:')
@@ -626,8 +646,7 @@ class Session:
         p = ops.make_pack_params(d['bases'], d['qualities'], d['N_qual'], d['bits_per_base'], d['bits_per_quality'],
                                  variable, d['dna_bytes_per_row'], d['quality_bytes_per_row'], d['dna_max'], self.hs.max_record_bytes,
                                  avg_record_bytes=self.d_buf.numel() // max(self.total, 1))
-        spec = getattr(self, '_spec', None)
-        self._spec = None
+        spec, self._spec = self._spec, None
         self.pack_path = 'speculative' if (spec is not None and ops.same_pack_params(p, spec[0])) else 'plain'
         if self.pack_path == 'speculative':
             dna, qual, bad = spec[1:]            # packed while the statistics were counted: the guess was right
@@ -683,12 +702,12 @@ class Session:
 
     @property
     def device_sizer(self):
-        return bool(getattr(self.args, 'device_compressor', False))
+        return bool(self.args.device_compressor)
 
     @property
     def bgzf_level(self):
         """--bgzf-level: the level of every run of the device compressor and of its host twin (1 when not given)."""
-        return getattr(self.args, 'bgzf_level', None) or 1
+        return self.args.bgzf_level or 1
 
     @property
     def has_compressor(self):
@@ -865,30 +884,34 @@ class Session:
         return all_results
 
     # ------------------------------------------------------------------ container
-    def write_container(self, path):
-        """uq.py:897-913: config.json + members into an uncompressed tar (members in numeric order, Q6)."""
+    def closing_config(self):
+        """uq.py:897-900: config.json with the parameters of the tables as it is written, and the member names in their order (numeric, Q6)."""
         args = self.args
         cfg = dict(self.config)
         cfg['sort'] = args.sort if isinstance(args.sort, str) else [None]
         cfg['raw'] = sorted(args.raw, key=str) if args.raw else [None]
         cfg['pattern'] = list(args.pattern) if args.pattern else None
         self.config = cfg
-        blob = json.dumps(cfg, indent=4, sort_keys=True).encode()
 
         def order(name):
             base = name.split('.')[0]
             if base.startswith('QNAME_'): return (3, int(base[6:]), name)
             return ({'DNA': 0, 'QUAL': 1, 'QNAME': 2}.get(base, 4), 0, name)
+        return json.dumps(cfg, indent=4, sort_keys=True).encode(), sorted(self.members, key=order)
 
+    def write_container(self, path):
+        """uq.py:897-913: config.json + members into an uncompressed tar."""
+        args = self.args
+        blob, names = self.closing_config()
         # private temp dir (Q5); beside the output unless --temp says otherwise, so the final move is a rename
-        tmpdir = tempfile.mkdtemp(prefix='uq_', dir=args.temp if getattr(args, 'temp', None) else (os.path.dirname(os.path.abspath(path)) or None))
+        tmpdir = tempfile.mkdtemp(prefix='uq_', dir=args.temp if args.temp else (os.path.dirname(os.path.abspath(path)) or None))
 
         def pwrite_all(fd, data, pos):
             mv = memoryview(data).cast('B')
             done = 0
             while done < len(mv): done += os.pwrite(fd, mv[done:], pos + done)
 
-        entries = [('config.json', (blob, np.zeros(0, np.uint8)))] + [(k, self.members[k]) for k in sorted(self.members, key=order)]
+        entries = [('config.json', (blob, np.zeros(0, np.uint8)))] + [(k, self.members[k]) for k in names]
         mtime = int(time.time()) if self.tar_mtime is None else int(self.tar_mtime)
         try:
             tmp = os.path.join(tmpdir, 'temp.uq')
@@ -896,7 +919,7 @@ class Session:
             # two zero blocks, padding to RECORDSIZE), with the payloads streamed HBM -> pinned -> pwrite.
             fd = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             try:
-                if getattr(args, 'gz', False): self.write_gz(fd, entries, mtime, pwrite_all)
+                if args.gz: self.write_gz(fd, entries, mtime, pwrite_all)
                 else: self.write_plain(fd, entries, mtime, pwrite_all)
             finally:
                 os.close(fd)
@@ -957,19 +980,22 @@ class Session:
     # ------------------------------------------------------------------ whole encode
     def encode(self):
         args = self.args
-        if args.output is None: args.output = args.input + ('.uQ.gz' if getattr(args, 'gz', False) else '.uQ')
+        if args.output is None: args.output = args.input + ('.uQ.gz' if args.gz else '.uQ')
         self.say('Warming up...')
         self.load_input()
         self.encode_loaded()
-        return self.verify() if getattr(args, 'verify', False) else True
+        return self.verify() if args.verify else True
 
     # ------------------------------------------------------------------ the record fingerprint
-    def fingerprint_input(self):
-        """--fingerprint: the input FASTQ (plain, BGZF or other gzip) goes to HBM as for an encode, only the record index is built; one JSON
-        line, no container."""
+    def indexed_input(self):
+        """The input FASTQ (plain, BGZF or other gzip) in HBM as for an encode, only the record index built: what ops.fingerprint and ops.qc take."""
         self.index_only = True
         self.load_input()
-        fp = self.ops.fingerprint(self.ctx, self.d_buf, self.d_ls, self.total)
+        return self.ctx, self.d_buf, self.d_ls, self.total
+
+    def fingerprint_input(self):
+        """--fingerprint: one JSON line, no container."""
+        fp = self.ops.fingerprint(*self.indexed_input())
         print(self.ops.fingerprint_json(fp), file=self.out)
         return fp
 
@@ -982,9 +1008,7 @@ class Session:
     # ------------------------------------------------------------------ the per-cycle tables
     def qc_input(self):
         """--qc: the input FASTQ goes to HBM as for --fingerprint (with --bin-qual it is binned there first); one kernel, one JSON line, no container."""
-        self.index_only = True
-        self.load_input()
-        qc = self.ops.qc(self.ctx, self.d_buf, self.d_ls, self.total, ncycles=self.args.qc_cycles or self.ops.QC_MAX_CYCLES)
+        qc = self.ops.qc(*self.indexed_input(), ncycles=self.args.qc_cycles or self.ops.QC_MAX_CYCLES)
         print(self.ops.qc_json(qc), file=self.out)
         return qc
 
@@ -1023,7 +1047,7 @@ class Session:
                 key + ' fingerprint equal', hx(got['records']))
             if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
             if self.pairing is not None: line += '; %d pairs, mates interleaved' % self.pairing['pairs']
-            if getattr(args, 'bin_qual', None) is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
+            if args.bin_qual is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
                 line += '; qualities binned by --bin-qual %s, %d characters changed' % (args.bin_qual, self.binned_changed_in_file())
             show(line)
             return True
@@ -1200,7 +1224,7 @@ class Session:
     def decode_text(self, config, DNA, QUAL, d_cols):
         """uq.py:1002-1058 on the device: the FASTQ text of these reads as one uint8 device tensor."""
         ops, ctx, n = self.ops, self.ctx, DNA[1]
-        if getattr(self.args, 'two_pass_decode', False):
+        if self.args.two_pass_decode:
             seq, qt, ln = self.split_bits(DNA, QUAL, config)
             return ops.emit_fastq(ctx, config, d_cols, seq, qt, ln, n)
         # rows -> text in one kernel (uq_decode_fastq)
@@ -1267,7 +1291,7 @@ class Session:
     def write_text(self, config, DNA, QUAL, d_cols, w):
         """The FASTQ text of these tables into the binary stream w (--bgzf: BGZF-compressed)."""
         ctx = self.ctx
-        bgzf = getattr(self.args, 'bgzf', False)
+        bgzf = self.args.bgzf
         if self.device_text_possible(config):
             # the text streams out through the pinned buffers (--bgzf: deflated on the device first)
             text = self.decode_text(config, DNA, QUAL, d_cols)
@@ -1345,13 +1369,13 @@ def main(argv=None):
         t_ready = time.perf_counter()                                # interpreter, torch and the device context are up
         ok = True
         if args.decode:
-            if getattr(args, 'fingerprint', False): s.fingerprint_decoded()
-            elif getattr(args, 'qc', False): s.qc_decoded()
-            elif getattr(args, 'split_mates', None): s.decode_split(*args.split_mates)
+            if args.fingerprint: s.fingerprint_decoded()
+            elif args.qc: s.qc_decoded()
+            elif args.split_mates: s.decode_split(*args.split_mates)
             else: s.decode()
-        elif getattr(args, 'fingerprint', False):
+        elif args.fingerprint:
             s.fingerprint_input()
-        elif getattr(args, 'qc', False):
+        elif args.qc:
             s.qc_input()
         else:
             ok = s.encode()
