@@ -217,6 +217,53 @@ int uq_mate_check_host(const uint8_t* h_a, const uint64_t* h_ls_a, uint64_t firs
                        const uint8_t* h_b, const uint64_t* h_ls_b, uint64_t first_b, uint64_t step_b,
                        uint64_t npairs, uint64_t pair_index_base, uq_mate_report* h_report);
 
+/* ---- read filtering (`--filter`; an extension: the reference stores every read it is given).  A filtered container is
+ * the plain encode of the filtered text.  All arithmetic is unsigned 64-bit; mix and K are the fingerprint's (uqfp1, above), cls and q the QC
+ * tables' (uqqc1, above): N is cls == 4, that is 'N' or 'n', and q(b) = clamp(b - 33, 0, 93).
+ * A record with the sequence line s (length Ls) and the quality line u (length Lu), both without their '\n', has the global index
+ * g = read_index_base + i and belongs to unit w = g / unit; unit is 1 for single reads and 2 for interleaved pairs.  Its VERDICT is a byte,
+ * the OR of
+ *    1  min_len   Ls < min_len
+ *    2  max_len   Ls > max_len
+ *    4  max_n     #{p < Ls : cls(s[p]) == 4} > max_n
+ *    8  mean_q    SUM_p q(u[p]) < min_mean_q * Lu   (an empty quality line passes)
+ *   16  sample    flags & UQ_FILTER_SAMPLE and mix(seed + K (w + 1)) >= sample_threshold
+ * The sample bit depends on w alone: both mates of a pair share it, and shards and pieces agree.  Criteria are switched off by min_len = 0,
+ * max_len = max_n = UINT32_MAX, min_mean_q = 0 and the sample flag clear.  A unit is KEPT iff the verdicts of all its records are 0.  The
+ * FILTERED TEXT is the kept units' bytes [ls[4 r0], ls[4 (r0 + unit)]), in input order, back to back from byte 0.
+ * uq_filter_report (device, 8-byte aligned; uq_filter_report_init zeroes it): every field is a sum, so calls and shards add.
+ * uq_filter_mark writes d_verdict[i] for record first_read + i, i < nreads, and ADDS reads_in, bases_in (SUM Ls), bytes_in and each fail_* once
+ *   per record with that bit set (a record can count under several).  It reads the records and 32 B of line starts per record and writes the
+ *   verdicts and the report, nothing else; queued on the context's stream, nothing read back.
+ * uq_filter_plan (nreads % unit == 0) writes, for the kept units j = 0 .. kept - 1 in input order, d_src[j] = the unit's byte offset in the
+ *   source, d_dst[j] = its offset in the output, and d_dst[kept] = the output's size; d_src holds nreads / unit entries, d_dst one more.  ADDS
+ *   reads_out, bases_out, bytes_out and fail_mate (the records with verdict 0 whose unit is dropped) to the report; hands back the two counts
+ *   (synchronises).
+ * uq_compact_records copies unit j's bytes [src[j], src[j] + dst[j + 1] - dst[j]) of d_buf to d_out + dst[j] (dst[0] = 0, ascending, a unit is
+ *   at least 4 bytes: what uq_filter_plan writes).  out_capacity < dst[kept_units] is an error before anything is launched on the buffers;
+ *   kept_units == 0 is a no-op; d_out must not overlap d_buf.  Nothing outside [0, dst[kept_units]) of d_out is written (16-byte stores at
+ *   aligned addresses, single bytes at the output's two ends), nothing outside the units -- so nothing outside [0, nbytes) -- of d_buf is read.
+ * Any buffer alignment; lines shorter than 2^32 bytes; 64-bit offsets everywhere.  unit not 1 or 2, nreads or read_index_base odd with unit 2,
+ * min_len > max_len and min_mean_q > 93 are errors.  The _host forms: the same, sequentially, on host memory (need no GPU). */
+#define UQ_FILTER_SAMPLE 1u
+typedef struct uq_filter_params { uint32_t min_len, max_len, max_n, min_mean_q; uint64_t sample_threshold, seed; uint32_t unit, flags; } uq_filter_params;
+typedef struct uq_filter_report { uint64_t reads_in, bases_in, bytes_in, reads_out, bases_out, bytes_out,
+                                  fail_min_len, fail_max_len, fail_max_n, fail_mean_q, fail_sample, fail_mate; } uq_filter_report;
+int uq_filter_report_init(uq_ctx* ctx, uq_filter_report* d_report);
+int uq_filter_report_init_host(uq_filter_report* h_report);
+int uq_filter_mark(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                   uint64_t read_index_base, const uq_filter_params* h_params, uint8_t* d_verdict, uq_filter_report* d_report);
+int uq_filter_mark_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                        uint64_t read_index_base, const uq_filter_params* h_params, uint8_t* h_verdict, uq_filter_report* h_report);
+int uq_filter_plan(uq_ctx* ctx, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads, uint32_t unit, const uint8_t* d_verdict,
+                   uint64_t* d_src, uint64_t* d_dst, uq_filter_report* d_report, uint64_t* h_kept_units, uint64_t* h_out_bytes);
+int uq_filter_plan_host(const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads, uint32_t unit, const uint8_t* h_verdict,
+                        uint64_t* h_src, uint64_t* h_dst, uq_filter_report* h_report, uint64_t* h_kept_units, uint64_t* h_out_bytes);
+int uq_compact_records(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_src, const uint64_t* d_dst, uint64_t kept_units,
+                       uint8_t* d_out, uint64_t out_capacity);
+int uq_compact_records_host(const uint8_t* h_buf, uint64_t nbytes, const uint64_t* h_src, const uint64_t* h_dst, uint64_t kept_units,
+                            uint8_t* h_out, uint64_t out_capacity);
+
 /* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

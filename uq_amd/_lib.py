@@ -101,6 +101,16 @@ class MateReport(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ('pairs', 'mismatches', 'first_mismatch', 'slash_pairs')]
 
 
+class FilterParams(C.Structure):
+    _fields_ = [('min_len', C.c_uint32), ('max_len', C.c_uint32), ('max_n', C.c_uint32), ('min_mean_q', C.c_uint32),
+                ('sample_threshold', C.c_uint64), ('seed', C.c_uint64), ('unit', C.c_uint32), ('flags', C.c_uint32)]
+
+
+class FilterReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('reads_in', 'bases_in', 'bytes_in', 'reads_out', 'bases_out', 'bytes_out',
+                                          'fail_min_len', 'fail_max_len', 'fail_max_n', 'fail_mean_q', 'fail_sample', 'fail_mate')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -153,6 +163,14 @@ SIGNATURES = {
     'uq_mate_report_init': [_vp, _vp],
     'uq_mate_check': [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _vp],
     'uq_mate_check_host': [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64, _P(MateReport)],
+    'uq_filter_report_init': [_vp, _vp],
+    'uq_filter_report_init_host': [_P(FilterReport)],
+    'uq_filter_mark': [_vp, _vp, _vp, _u64, _u64, _u64, _P(FilterParams), _vp, _vp],
+    'uq_filter_mark_host': [_vp, _vp, _u64, _u64, _u64, _P(FilterParams), _vp, _P(FilterReport)],
+    'uq_filter_plan': [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _vp, _vp, _P(_u64), _P(_u64)],
+    'uq_filter_plan_host': [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _P(FilterReport), _P(_u64), _P(_u64)],
+    'uq_compact_records': [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64],
+    'uq_compact_records_host': [_vp, _u64, _vp, _vp, _u64, _vp, _u64],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

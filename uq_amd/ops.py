@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -474,6 +474,97 @@ def mate_check_host(a, b, first_a=0, step_a=1, first_b=0, step_b=1, npairs=None,
     d = {k: int(getattr(r, k)) for k in MATE_REPORT_FIELDS}
     if d['first_mismatch'] == UQ_NONE: d['first_mismatch'] = None
     return d
+
+
+# ------------------------------------------------------------------ read filtering (include/uqhip.h)
+FILTER_REPORT_FIELDS = tuple(k for k, _ in FilterReport._fields_)
+FILTER_SAMPLE = 1
+FILTER_OFF = {'min_len': 0, 'max_len': 0xFFFFFFFF, 'max_n': 0xFFFFFFFF, 'min_mean_q': 0, 'sample_threshold': 0, 'seed': 0, 'flags': 0}
+
+
+def filter_params(unit=1, **criteria):
+    """A uq_filter_params: every criterion off but the ones given (min_len, max_len, max_n, min_mean_q; sample_threshold + seed + flags)."""
+    unknown = set(criteria) - set(FILTER_OFF)
+    if unknown: raise ValueError('filter: unknown criteria %s' % sorted(unknown))
+    d = dict(FILTER_OFF, **criteria)
+    return FilterParams(d['min_len'], d['max_len'], d['max_n'], d['min_mean_q'], d['sample_threshold'], d['seed'], unit, d['flags'])
+
+
+def filter_report_new(ctx):
+    """A zeroed device uq_filter_report (int64[12])."""
+    t = ctx.torch
+    d = t.empty(len(FILTER_REPORT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_filter_report_init', ctx.h, _p(d))
+    return d
+
+
+def filter_report_fetch(ctx, d_report):
+    """The device report as a dict of Python integers (synchronises)."""
+    return dict(zip(FILTER_REPORT_FIELDS, (int(v) for v in ctx.to_numpy(d_report).view(np.uint64))))
+
+
+def filter_mark(ctx, d_report, buf, line_start, first_read, nreads, params, index_base=0, verdict=None):
+    """The verdict bytes of the records [first_read, first_read + nreads) of buf (a new uint8 tensor when `verdict` is None), their counts
+    added into d_report (queued, nothing read back)."""
+    if verdict is None: verdict = ctx.empty(nreads)
+    call('uq_filter_mark', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), int(index_base), C.byref(params), _p(verdict), _p(d_report))
+    return verdict
+
+
+def filter_plan(ctx, d_report, line_start, first_read, nreads, unit, verdict):
+    """The kept units of the records as (src, dst, kept units, output bytes): src[j] / dst[j] the unit's offsets in the source and in the
+    output, dst[kept] the output's size (int64 tensors holding u64 of nreads / unit and one more entries; synchronises)."""
+    t = ctx.torch
+    src = t.empty(nreads // unit, dtype=t.int64, device=ctx.device)
+    dst = t.empty(nreads // unit + 1, dtype=t.int64, device=ctx.device)
+    kept, size = C.c_uint64(0), C.c_uint64(0)
+    call('uq_filter_plan', ctx.h, _p(line_start), int(first_read), int(nreads), int(unit), _p(verdict), _p(src), _p(dst), _p(d_report),
+         C.byref(kept), C.byref(size))
+    return src, dst, kept.value, size.value
+
+
+def compact_records(ctx, buf, src, dst, kept_units, out=None, out_capacity=None, out_bytes=None):
+    """The kept units of buf back to back from byte 0 of `out` on (queued; a new uint8 tensor of out_bytes when `out` is None).
+    out_capacity: what the library is told `out` holds (its numel by default)."""
+    if out is None: out = ctx.empty(out_bytes)
+    call('uq_compact_records', ctx.h, _p(buf), int(buf.numel()), _p(src), _p(dst), int(kept_units), _p(out),
+         int(out.numel() if out_capacity is None else out_capacity))
+    return out
+
+
+def filter_mark_host(data, params, line_start=None, first_read=0, nreads=None, index_base=0, report=None):
+    """uq_filter_mark_host: the same on the CPU over host bytes (needs no GPU) -> (uint8 verdicts, report dict; `report`: an earlier one to add to)."""
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'filter')
+    r = FilterReport(*[report[k] for k in FILTER_REPORT_FIELDS]) if report is not None else FilterReport()
+    verdict = np.empty(nreads, dtype=np.uint8)
+    call('uq_filter_mark_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(index_base),
+         C.byref(params), C.c_void_p(verdict.ctypes.data if nreads else 0), C.byref(r))
+    return verdict, {k: int(getattr(r, k)) for k in FILTER_REPORT_FIELDS}
+
+
+def filter_plan_host(line_start, verdict, unit=1, first_read=0, report=None):
+    """uq_filter_plan_host -> (src, dst, kept units, output bytes, report dict); src / dst are uint64 arrays cut to kept and kept + 1 entries."""
+    ls = np.ascontiguousarray(line_start, dtype=np.uint64)
+    verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+    nreads = len(verdict)
+    if first_read < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('filter: records beyond the index')
+    r = FilterReport(*[report[k] for k in FILTER_REPORT_FIELDS]) if report is not None else FilterReport()
+    src, dst = np.zeros(nreads // unit if unit in (1, 2) else 0, dtype=np.uint64), np.zeros((nreads // unit if unit in (1, 2) else 0) + 1, dtype=np.uint64)
+    kept, size = C.c_uint64(0), C.c_uint64(0)
+    call('uq_filter_plan_host', C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(unit), C.c_void_p(verdict.ctypes.data if nreads else 0),
+         C.c_void_p(src.ctypes.data if src.size else 0), C.c_void_p(dst.ctypes.data), C.byref(r), C.byref(kept), C.byref(size))
+    return src[:kept.value], dst[:kept.value + 1], kept.value, size.value, {k: int(getattr(r, k)) for k in FILTER_REPORT_FIELDS}
+
+
+def compact_records_host(data, src, dst, kept_units, out_capacity=None):
+    """uq_compact_records_host: the kept units of host bytes as a new uint8 array (needs no GPU)."""
+    a = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src, dst = np.ascontiguousarray(src, dtype=np.uint64), np.ascontiguousarray(dst, dtype=np.uint64)
+    size = int(dst[kept_units]) if kept_units else 0
+    out = np.empty(size, dtype=np.uint8)
+    call('uq_compact_records_host', C.c_void_p(a.ctypes.data if a.size else 0), int(a.size), C.c_void_p(src.ctypes.data if src.size else 0),
+         C.c_void_p(dst.ctypes.data), int(kept_units), C.c_void_p(out.ctypes.data if out.size else 0), size if out_capacity is None else int(out_capacity))
+    return out
 
 
 # ------------------------------------------------------------------ pack

@@ -99,6 +99,8 @@ def build_parser():
                    help='with --qc: the number of exact cycles, 1 .. 1024 (the default); positions from N on are counted together under "beyond" (extension)')
     from . import binqual
     p.add_argument('--bin-qual', action='store', default=None, metavar='SPEC', help=binqual.HELP)
+    from . import recfilter
+    p.add_argument('--filter', action='store', default=None, metavar='SPEC', help=recfilter.HELP)
     p.add_argument('--mate2', action='store', default=None, metavar='R2.fastq',
                    help='paired-end input: -i is R1, this is R2 (plain, BGZF or other gzip, each by its content).  The read counts must be equal and '
                         'read r of R2 must be the mate of read r of R1 (same QNAME up to the first space or tab, /1 with /2 allowed); the two '
@@ -159,6 +161,9 @@ def validate_args(args):
     if args.bin_qual is not None:
         if args.decode: error('ERROR: --bin-qual changes the qualities an encode stores: the text --decode writes is what the container holds')
         bin_qual_table(args.bin_qual)
+    if args.filter is not None:
+        if args.decode: error('ERROR: --filter drops reads before an encode stores them: the text --decode writes is what the container holds')
+        filter_criteria(args.filter)
     mate2, interleaved, split = args.mate2, args.interleaved, args.split_mates
     if mate2 is not None and interleaved:
         error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
@@ -180,6 +185,12 @@ def bin_qual_table(spec):
     """--bin-qual SPEC -> (the 256-byte table, the explicit form of the spec); a bad spec is a UqError."""
     from . import binqual
     return binqual.parse(spec), binqual.explicit(spec)
+
+
+def filter_criteria(spec):
+    """--filter SPEC -> (the criteria of uq_filter_params, the explicit form of the spec); a bad spec is a UqError."""
+    from . import recfilter
+    return recfilter.parse(spec), recfilter.explicit(spec)
 
 
 def npy_header(shape, fortran_order, dtype):
@@ -229,6 +240,8 @@ class Session:
         self.pairing = None        # --mate2 / --interleaved: config.json's "paired" value
         self.bin_qual_ranges = None    # --bin-qual: the explicit form of the spec
         self.binned_changed = 0    # --bin-qual: quality characters this session's binning changed
+        self.filtering = None      # --filter: config.json's "filter" value (spec, criteria, unit, report)
+        self._pre_index = None     # --filter: (reads, record index) of the buffer a paired loader hands load_device, until filter_records takes it
         self.d_buf = None          # the FASTQ text in HBM (uint8 device tensor)
         self.total = 0             # reads in d_buf
         self.d = None              # analyse: the decisions of analysis.decide_from_stats
@@ -275,14 +288,14 @@ class Session:
             if 'c' not in census: census['c'] = ops.ChunkedCensus(ctx, d)
             census['c'].chunk(lo, n)
         chunked = self.io.chunk % (16 << 10) == 0
-        d_buf = self.io.file_to_device(path, on_chunk=on_chunk if chunked else None)
-        self.load_device(d_buf, census=census.get('c'))
+        self.d_buf = self.io.file_to_device(path, on_chunk=on_chunk if chunked else None)
+        self.load_device(census=census.get('c'))       # (the text is handed over in `d_buf`, no name of it kept here: --filter frees it)
 
     def load_gzip(self, path):
         """gzip input (an extension: the reference reads plain text only), recognised by its magic bytes: gzip_to_device, then load_device."""
-        d_buf = self.gzip_to_device(path)
+        self.d_buf = self.gzip_to_device(path)
         self.path, self._host = None, None             # the file holds compressed bytes: the host copy (`host`) comes from d_buf
-        self.load_device(d_buf)
+        self.load_device()
 
     def gzip_to_device(self, path):
         """A gzip file's text as a device buffer.  BGZF (every member carries its
@@ -332,8 +345,22 @@ class Session:
         """The input of an encode (or of --fingerprint / --qc) in HBM: one file, two mates interleaved on the device, or one interleaved file."""
         args = self.args
         if args.mate2 is not None: return self.load_pairs(args.input, args.mate2)
+        if args.interleaved and args.filter is not None: return self.load_interleaved_filtered(args.input)
         self.load(args.input)
         if args.interleaved: self.check_interleaved()
+
+    def load_interleaved_filtered(self, path):
+        """--interleaved --filter: the mates are checked on the input as it is given, BEFORE load_device drops reads: text to HBM, index, even
+        read count, uq_mate_check, then load_device (which filters, and checks the mates of what is left once more)."""
+        d_buf = self.text_to_device(path)
+        n, ls = self.indexed(d_buf, None)
+        if n % 2: error('ERROR: --interleaved: the input holds %d reads, an odd number: R1 and R2 do not alternate' % n)
+        self.require_mates(d_buf, ls, 0, 2, d_buf, ls, 1, 2, n // 2)
+        self.path, self._host = None, None
+        self._pre_index = (n, ls)
+        self.d_buf = d_buf
+        del d_buf, ls
+        self.load_device()
 
     def indexed(self, d_buf, what):
         """(reads, record index) of a text in HBM."""
@@ -371,20 +398,27 @@ class Session:
         ctx.sync()
         del d_1, d_2, ls_1, ls_2
         self.path, self._host = None, None             # no file holds the interleaved bytes: the host copy (`host`) comes from d_buf
-        self.load_device(d_out)
+        self.d_buf = d_out
+        del d_out
+        self.load_device()
 
     def check_interleaved(self):
         """--interleaved, behind `load`: an even read count, and record 2i + 1 the mate of record 2i (one buffer, nothing copied)."""
         if self.total % 2: error('ERROR: --interleaved: the input holds %d reads, an odd number: R1 and R2 do not alternate' % self.total)
         self.require_mates(self.d_buf, self.d_ls, 0, 2, self.d_buf, self.d_ls, 1, 2, self.total // 2)
 
-    def load_device(self, d_buf, census=None):
+    def load_device(self, d_buf=None, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
         all been queued -- load() queues them behind the PCIe copies).  --bin-qual first; then the line count alone (--fingerprint, --qc),
         or the queued step bench.py times, or -- where that does not hold for this file -- the same two reads with the record index,
         or -- where that has no kernel either, and under --multi-pass -- the plain statistics pass.  Same results whichever path."""
         self._reset_load_state()
-        self.d_buf = d_buf
+        if d_buf is not None: self.d_buf = d_buf         # (the loaders of this class leave the text in `d_buf` and pass none: --filter can then free it)
+        del d_buf
+        if self.args.filter is not None:
+            self.filter_records(census)
+            census = None                                # (the kept reads in a buffer of their own; the census of the unfiltered text has been closed)
+        d_buf = self.d_buf
         binned = self.bin_qualities(census) if self.args.bin_qual is not None else None      # (line count, record index)
         if binned is not None: census = None             # (its census has been closed; the step below runs its own: one more census per encode, with the flag only)
         if self.index_only: return self._load_index_only(census, binned)
@@ -468,6 +502,39 @@ class Session:
         """--multi-pass, and whatever the speculative forms left: the statistics as a pass of their own over the record index."""
         self.d_stats = self.ops.stats_new(self.ctx)
         self.ops.stats_accumulate(self.ctx, self.d_stats, self.d_buf, self.d_ls, 0, self.total)
+
+    def filter_records(self, census=None):
+        """--filter, at the head of load_device, in front of bin_qualities (the mean quality is judged on the qualities as given): the records
+        of self.d_buf get their verdicts (uq_filter_mark), the kept units their places (uq_filter_plan; a unit is a pair under --mate2 /
+        --interleaved) and are copied back to back into a new buffer (uq_compact_records), which replaces self.d_buf; the old one is freed.
+        Needs the record index (the census, closed here if load() had begun one, + uq_index_lines -- or what a paired loader left in
+        `_pre_index`).  Nothing kept is a refusal before anything is written.  Of a paired text the mates are checked once more on what is
+        left, and that report is what `pairing` holds."""
+        ops, ctx, args = self.ops, self.ctx, self.args
+        d_buf = self.d_buf
+        criteria, explicit = filter_criteria(args.filter)
+        unit = 2 if (args.mate2 is not None or args.interleaved) else 1
+        if self._pre_index is not None: (n, ls), self._pre_index = self._pre_index, None
+        else:
+            nlines = census.end() if census is not None else (ops.count_lines(ctx, d_buf) if d_buf.numel() else 0)
+            if census is not None: census.buf = None     # (closed: it lets go of the unfiltered text)
+            n = whole_records(nlines)
+            ls = ops.index_lines(ctx, d_buf, nlines)
+        if n % unit: error('ERROR: --interleaved: the input holds %d reads, an odd number: R1 and R2 do not alternate' % n)
+        d_report = ops.filter_report_new(ctx)
+        verdict = ops.filter_mark(ctx, d_report, d_buf, ls, 0, n, ops.filter_params(unit=unit, **criteria))
+        src, dst, kept, size = ops.filter_plan(ctx, d_report, ls, 0, n, unit, verdict)
+        report = ops.filter_report_fetch(ctx, d_report)
+        if kept == 0: error('ERROR: --filter %s keeps none of the %d reads' % (args.filter, n))
+        d_out = ops.compact_records(ctx, d_buf, src, dst, kept, out_bytes=size)
+        ctx.sync()
+        self.d_buf = d_out
+        del d_buf, src, dst, verdict, ls               # the unfiltered text is freed here: the loaders of this class keep no name of it (a caller that passed its own tensor to load_device keeps that)
+        self.path, self._host = None, None             # no file holds the filtered bytes: the host copy (`host`) comes from d_buf
+        self.filtering = {'spec': args.filter, 'criteria': explicit, 'unit': unit, 'report': report}
+        if unit == 2:
+            nk, ls_k = self.indexed(d_out, None)
+            self.require_mates(d_out, ls_k, 0, 2, d_out, ls_k, 1, 2, nk // 2)
 
     def bin_qualities(self, census=None):
         """--bin-qual, at the head of load_device: the table of the spec applied to every quality line of self.d_buf, in place
@@ -582,6 +649,9 @@ class Session:
             binning = {'spec': args.bin_qual, 'ranges': self.bin_qual_ranges or bin_qual_table(args.bin_qual)[1],
                        'changed': self.binned_changed_in_file()}
             self.say('Binned qualities (%s): %d of %d quality characters changed' % (args.bin_qual, binning['changed'], sum(d['qual_distribution'].values())))
+        if self.filtering is not None:
+            from . import recfilter
+            self.say(recfilter.report_line(self.filtering['report']))
         self.report(prefix, suffix, separators)
         self.config = {
             'base_distribution': d['base_distribution'], 'qual_distribution': d['qual_distribution'],
@@ -591,6 +661,7 @@ class Session:
             'QNAME_prefix': prefix, 'QNAME_suffix': suffix, 'QNAME_separators': separators, 'QNAME_columns': columns,
         }
         if binning is not None: self.config['quality_binning'] = binning
+        if self.filtering is not None: self.config['filter'] = dict(self.filtering)
         if self.pairing is not None: self.config['paired'] = dict(self.pairing)
 
     def report(self, prefix, suffix, separators):
@@ -1047,6 +1118,8 @@ class Session:
                 key + ' fingerprint equal', hx(got['records']))
             if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
             if self.pairing is not None: line += '; %d pairs, mates interleaved' % self.pairing['pairs']
+            if self.filtering is not None:                    # `want` was taken from the filtered text in HBM
+                line += '; gives back the %d reads --filter kept of %d' % (self.filtering['report']['reads_out'], self.filtering['report']['reads_in'])
             if args.bin_qual is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
                 line += '; qualities binned by --bin-qual %s, %d characters changed' % (args.bin_qual, self.binned_changed_in_file())
             show(line)
