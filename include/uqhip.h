@@ -264,6 +264,58 @@ int uq_compact_records(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, const
 int uq_compact_records_host(const uint8_t* h_buf, uint64_t nbytes, const uint64_t* h_src, const uint64_t* h_dst, uint64_t kept_units,
                             uint8_t* h_out, uint64_t out_capacity);
 
+/* ---- read trimming (`--trim`; an extension: the reference stores every read as it is given).  A trimmed container is
+ * the plain encode of the trimmed text.  cls and q are the QC tables' (uqqc1, above): G is cls == 2 ('G' or 'g'), N is cls == 4 ('N' or 'n'),
+ * q(b) = clamp(b - 33, 0, 93).  A record has the lines qn, s, p, u without their '\n' (a '\r' in front of a '\n' is the line's last byte, as
+ * everywhere), Ls = len(s), Lu = len(u).  If Ls != Lu the record is copied unchanged: its WINDOW is (0, Ls), it counts once in len_mismatch and
+ * enters no cut_* sum.  Otherwise L = Ls and the window [a, b) is made in four steps, in this order:
+ *   1 fixed    a = min(head, L); b = L - min(tail, L - a); if crop != UINT32_MAX: b = min(b, a + crop); cut_fixed += L - (b - a).
+ *   2 poly-G   (polyg = G, 0 = off) g = the number of consecutive bytes with cls == 2 at the end of s[a, b); if G > 0 and g >= G: b -= g,
+ *              cut_polyg += g.
+ *   3 quality  (q3 = T3, q5 = T5, 0 = off, at most 93; the BWA / cutadapt running sum, signed 64-bit) both on the window [a, b) step 2 left,
+ *              independently of each other.
+ *              3' end: acc = 0, best = 0, b' = b; for i = b - 1 down to a: acc += T3 - q(u[i]); if acc < 0 stop; if acc > best: best = acc, b' = i.
+ *              5' end: acc = 0, best = 0, a' = a; for i = a up to b - 1: acc += T5 - q(u[i]); if acc < 0 stop; if acc > best: best = acc, a' = i + 1.
+ *              cut_q3 += b - b'; a'' = min(a', b'); cut_q5 += a'' - a; the window becomes [a'', b').
+ *              In closed form, with S_i = SUM_{j = i .. b - 1} (T3 - q(u[j])): stop = the largest i in [a, b) with S_i < 0 (a - 1 if there
+ *              is none); b' = the i in (stop, b) with the largest S_i > 0, the largest such i among equals (b if there is none).  The 5' form
+ *              is the mirror image.
+ *   4 N ends   (flags & UQ_TRIM_N) while a < b and cls(s[a]) == 4: a++; while b > a and cls(s[b - 1]) == 4: b--; cut_n += what was removed.
+ * The TRIMMED RECORD is qn '\n' s[a:b] '\n' p '\n' u[a:b] '\n'; the TRIMMED TEXT is the trimmed records in input order, back to back from byte 0.
+ * uq_trim_report (device, 8-byte aligned; uq_trim_report_init zeroes it): thirteen sums, so calls and shards add.  reads_trimmed = the records
+ *   whose window is not (0, Ls); emptied = the records with a == b and L > 0;  bases_in - bases_out = cut_fixed + cut_polyg + cut_q5 + cut_q3
+ *   + cut_n and bytes_in - bytes_out = 2 (bases_in - bases_out).
+ * uq_trim_mark writes d_window[2 i] = a, d_window[2 i + 1] = b for record first_read + i, i < nreads, and ADDS every field of the report.  It
+ *   reads the records and their line starts and writes the windows and the report, nothing else; queued on the context's stream, nothing
+ *   read back.
+ * uq_trim_plan writes d_dst[i] = the output offset of record first_read + i and d_dst[nreads] = the output's size (uq_scan_exclusive_u64), and
+ *   hands the size back (one read-back; synchronises).
+ * uq_trim_records writes the trimmed records to d_out (record first_read + i at d_dst[i]) and, when d_line_start_out is not NULL, the record
+ *   index of the trimmed text (4 nreads + 1 entries: what uq_index_lines would write for it).  out_capacity < dst[nreads] is an error before
+ *   anything is launched on the buffers; nreads == 0 is a no-op; d_out must not overlap d_buf.  Nothing outside [0, dst[nreads]) of d_out is
+ *   written (16-byte stores at aligned addresses, single bytes at the output's two ends), nothing outside the records of d_buf is read.
+ * Any buffer alignment; lines shorter than 2^32 bytes with their '\n'; 64-bit offsets everywhere.  q5 > 93, q3 > 93 and crop == 0 are errors.
+ * A window with a > b or b > Ls (or, where Ls != Lu, another one than (0, Ls)) handed to uq_trim_plan or uq_trim_records is an error in the
+ * _host forms and UNDEFINED on the device.  The _host forms: the same, sequentially, on host memory (need no GPU). */
+#define UQ_TRIM_N 1u
+typedef struct uq_trim_params { uint32_t head, tail, crop, polyg, q5, q3, flags, reserved; } uq_trim_params;
+typedef struct uq_trim_report { uint64_t reads_in, bases_in, bytes_in, reads_trimmed, bases_out, bytes_out,
+                                cut_fixed, cut_polyg, cut_q5, cut_q3, cut_n, emptied, len_mismatch; } uq_trim_report;
+int uq_trim_report_init(uq_ctx* ctx, uq_trim_report* d_report);
+int uq_trim_report_init_host(uq_trim_report* h_report);
+int uq_trim_mark(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                 const uq_trim_params* h_params, uint32_t* d_window, uq_trim_report* d_report);
+int uq_trim_mark_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                      const uq_trim_params* h_params, uint32_t* h_window, uq_trim_report* h_report);
+int uq_trim_plan(uq_ctx* ctx, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads, const uint32_t* d_window,
+                 uint64_t* d_dst, uint64_t* h_out_bytes);
+int uq_trim_plan_host(const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads, const uint32_t* h_window,
+                      uint64_t* h_dst, uint64_t* h_out_bytes);
+int uq_trim_records(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                    const uint32_t* d_window, const uint64_t* d_dst, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_line_start_out);
+int uq_trim_records_host(const uint8_t* h_buf, uint64_t nbytes, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                         const uint32_t* h_window, const uint64_t* h_dst, uint8_t* h_out, uint64_t out_capacity, uint64_t* h_line_start_out);
+
 /* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

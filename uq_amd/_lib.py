@@ -111,6 +111,15 @@ class FilterReport(C.Structure):
                                           'fail_min_len', 'fail_max_len', 'fail_max_n', 'fail_mean_q', 'fail_sample', 'fail_mate')]
 
 
+class TrimParams(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ('head', 'tail', 'crop', 'polyg', 'q5', 'q3', 'flags', 'reserved')]
+
+
+class TrimReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('reads_in', 'bases_in', 'bytes_in', 'reads_trimmed', 'bases_out', 'bytes_out',
+                                          'cut_fixed', 'cut_polyg', 'cut_q5', 'cut_q3', 'cut_n', 'emptied', 'len_mismatch')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -171,6 +180,14 @@ SIGNATURES = {
     'uq_filter_plan_host': [_vp, _u64, _u64, _u32, _vp, _vp, _vp, _P(FilterReport), _P(_u64), _P(_u64)],
     'uq_compact_records': [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64],
     'uq_compact_records_host': [_vp, _u64, _vp, _vp, _u64, _vp, _u64],
+    'uq_trim_report_init': [_vp, _vp],
+    'uq_trim_report_init_host': [_P(TrimReport)],
+    'uq_trim_mark': [_vp, _vp, _vp, _u64, _u64, _P(TrimParams), _vp, _vp],
+    'uq_trim_mark_host': [_vp, _vp, _u64, _u64, _P(TrimParams), _vp, _P(TrimReport)],
+    'uq_trim_plan': [_vp, _vp, _u64, _u64, _vp, _vp, _P(_u64)],
+    'uq_trim_plan_host': [_vp, _u64, _u64, _vp, _vp, _P(_u64)],
+    'uq_trim_records': [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
+    'uq_trim_records_host': [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

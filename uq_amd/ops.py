@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -565,6 +565,103 @@ def compact_records_host(data, src, dst, kept_units, out_capacity=None):
     call('uq_compact_records_host', C.c_void_p(a.ctypes.data if a.size else 0), int(a.size), C.c_void_p(src.ctypes.data if src.size else 0),
          C.c_void_p(dst.ctypes.data), int(kept_units), C.c_void_p(out.ctypes.data if out.size else 0), size if out_capacity is None else int(out_capacity))
     return out
+
+
+# ------------------------------------------------------------------ read trimming (include/uqhip.h)
+TRIM_REPORT_FIELDS = tuple(k for k, _ in TrimReport._fields_)
+TRIM_N = 1
+TRIM_OFF = {'head': 0, 'tail': 0, 'crop': 0xFFFFFFFF, 'polyg': 0, 'q5': 0, 'q3': 0, 'flags': 0}
+
+
+def trim_params(**steps):
+    """A uq_trim_params: every step off but the ones given (head, tail, crop, polyg, q5, q3, flags)."""
+    unknown = set(steps) - set(TRIM_OFF)
+    if unknown: raise ValueError('trim: unknown steps %s' % sorted(unknown))
+    d = dict(TRIM_OFF, **steps)
+    return TrimParams(d['head'], d['tail'], d['crop'], d['polyg'], d['q5'], d['q3'], d['flags'], 0)
+
+
+def trim_report_new(ctx):
+    """A zeroed device uq_trim_report (int64[13])."""
+    t = ctx.torch
+    d = t.empty(len(TRIM_REPORT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_trim_report_init', ctx.h, _p(d))
+    return d
+
+
+def trim_report_fetch(ctx, d_report):
+    """The device report as a dict of Python integers (synchronises)."""
+    return dict(zip(TRIM_REPORT_FIELDS, (int(v) for v in ctx.to_numpy(d_report).view(np.uint64))))
+
+
+def trim_mark(ctx, d_report, buf, line_start, first_read, nreads, params, window=None):
+    """The windows (a, b) of the records [first_read, first_read + nreads) of buf (a new int32 tensor of 2 nreads u32 when `window` is None),
+    their counts added into d_report (queued, nothing read back)."""
+    t = ctx.torch
+    if window is None: window = t.empty(2 * nreads, dtype=t.int32, device=ctx.device)
+    call('uq_trim_mark', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), C.byref(params), _p(window), _p(d_report))
+    return window
+
+
+def trim_plan(ctx, line_start, first_read, nreads, window, dst=None):
+    """(dst, output bytes): dst[i] the output offset of record first_read + i, dst[nreads] the output's size (an int64 tensor holding u64;
+    synchronises)."""
+    t = ctx.torch
+    if dst is None: dst = t.empty(nreads + 1, dtype=t.int64, device=ctx.device)
+    size = C.c_uint64(0)
+    call('uq_trim_plan', ctx.h, _p(line_start), int(first_read), int(nreads), _p(window), _p(dst), C.byref(size))
+    return dst, size.value
+
+
+def trim_records(ctx, buf, line_start, first_read, nreads, window, dst, out=None, out_capacity=None, out_bytes=None, index=False, line_start_out=None):
+    """The trimmed records back to back from byte 0 of `out` on (queued; a new uint8 tensor of out_bytes when `out` is None).  index=True: also the
+    record index of the trimmed text (int64[4 nreads + 1]) -> (out, index).  out_capacity: what the library is told `out` holds."""
+    t = ctx.torch
+    if out is None: out = ctx.empty(out_bytes)
+    if index and line_start_out is None: line_start_out = t.empty(4 * nreads + 1, dtype=t.int64, device=ctx.device)
+    call('uq_trim_records', ctx.h, _p(buf), int(buf.numel()), _p(line_start), int(first_read), int(nreads), _p(window), _p(dst), _p(out),
+         int(out.numel() if out_capacity is None else out_capacity), _p(line_start_out))
+    return (out, line_start_out) if index else out
+
+
+def trim_mark_host(data, params, line_start=None, first_read=0, nreads=None, report=None):
+    """uq_trim_mark_host: the same on the CPU over host bytes (needs no GPU) -> (uint32[nreads, 2] windows, report dict; `report`: an earlier
+    one to add to)."""
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'trim')
+    r = TrimReport(*[report[k] for k in TRIM_REPORT_FIELDS]) if report is not None else TrimReport()
+    window = np.zeros((nreads, 2), dtype=np.uint32)
+    call('uq_trim_mark_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
+         C.byref(params), C.c_void_p(window.ctypes.data if nreads else 0), C.byref(r))
+    return window, {k: int(getattr(r, k)) for k in TRIM_REPORT_FIELDS}
+
+
+def trim_plan_host(line_start, window, first_read=0):
+    """uq_trim_plan_host -> (dst uint64[nreads + 1], output bytes)."""
+    ls = np.ascontiguousarray(line_start, dtype=np.uint64)
+    window = np.ascontiguousarray(window, dtype=np.uint32).reshape(-1, 2)
+    nreads = len(window)
+    if first_read < 0 or 4 * (first_read + nreads) + 1 > len(ls): raise ValueError('trim: records beyond the index')
+    dst = np.zeros(nreads + 1, dtype=np.uint64)
+    size = C.c_uint64(0)
+    call('uq_trim_plan_host', C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), C.c_void_p(window.ctypes.data if nreads else 0),
+         C.c_void_p(dst.ctypes.data), C.byref(size))
+    return dst, size.value
+
+
+def trim_records_host(data, line_start, window, dst, first_read=0, out_capacity=None, index=False):
+    """uq_trim_records_host: the trimmed records of host bytes as a new uint8 array (needs no GPU); index=True: -> (array, its record index)."""
+    a, ls = _host_indexed(data, line_start)
+    window = np.ascontiguousarray(window, dtype=np.uint32).reshape(-1, 2)
+    dst = np.ascontiguousarray(dst, dtype=np.uint64)
+    nreads = len(window)
+    if first_read < 0 or 4 * (first_read + nreads) + 1 > len(ls) or len(dst) != nreads + 1: raise ValueError('trim: records beyond the index')
+    size = int(dst[nreads])
+    out = np.empty(size, dtype=np.uint8)
+    lso = np.zeros(4 * nreads + 1, dtype=np.uint64) if index else None
+    call('uq_trim_records_host', C.c_void_p(a.ctypes.data if a.size else 0), int(a.size), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
+         C.c_void_p(window.ctypes.data if nreads else 0), C.c_void_p(dst.ctypes.data), C.c_void_p(out.ctypes.data if out.size else 0),
+         size if out_capacity is None else int(out_capacity), C.c_void_p(lso.ctypes.data) if index else C.c_void_p(0))
+    return (out, lso) if index else out
 
 
 # ------------------------------------------------------------------ pack

@@ -101,6 +101,8 @@ def build_parser():
     p.add_argument('--bin-qual', action='store', default=None, metavar='SPEC', help=binqual.HELP)
     from . import recfilter
     p.add_argument('--filter', action='store', default=None, metavar='SPEC', help=recfilter.HELP)
+    from . import rectrim
+    p.add_argument('--trim', action='store', default=None, metavar='SPEC', help=rectrim.HELP)
     p.add_argument('--mate2', action='store', default=None, metavar='R2.fastq',
                    help='paired-end input: -i is R1, this is R2 (plain, BGZF or other gzip, each by its content).  The read counts must be equal and '
                         'read r of R2 must be the mate of read r of R1 (same QNAME up to the first space or tab, /1 with /2 allowed); the two '
@@ -164,6 +166,9 @@ def validate_args(args):
     if args.filter is not None:
         if args.decode: error('ERROR: --filter drops reads before an encode stores them: the text --decode writes is what the container holds')
         filter_criteria(args.filter)
+    if args.trim is not None:
+        if args.decode: error('ERROR: --trim cuts reads before an encode stores them: the text --decode writes is what the container holds')
+        trim_steps(args.trim)
     mate2, interleaved, split = args.mate2, args.interleaved, args.split_mates
     if mate2 is not None and interleaved:
         error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
@@ -191,6 +196,12 @@ def filter_criteria(spec):
     """--filter SPEC -> (the criteria of uq_filter_params, the explicit form of the spec); a bad spec is a UqError."""
     from . import recfilter
     return recfilter.parse(spec), recfilter.explicit(spec)
+
+
+def trim_steps(spec):
+    """--trim SPEC -> (the steps of uq_trim_params, the explicit form of the spec); a bad spec is a UqError."""
+    from . import rectrim
+    return rectrim.parse(spec), rectrim.explicit(spec)
 
 
 def npy_header(shape, fortran_order, dtype):
@@ -241,7 +252,8 @@ class Session:
         self.bin_qual_ranges = None    # --bin-qual: the explicit form of the spec
         self.binned_changed = 0    # --bin-qual: quality characters this session's binning changed
         self.filtering = None      # --filter: config.json's "filter" value (spec, criteria, unit, report)
-        self._pre_index = None     # --filter: (reads, record index) of the buffer a paired loader hands load_device, until filter_records takes it
+        self.trimming = None       # --trim: config.json's "trim" value (spec, criteria, report)
+        self._pre_index = None     # --trim, --filter: (reads, record index) of the buffer a paired loader or trim_records hands on, until the next step of load_device takes it
         self.d_buf = None          # the FASTQ text in HBM (uint8 device tensor)
         self.total = 0             # reads in d_buf
         self.d = None              # analyse: the decisions of analysis.decide_from_stats
@@ -409,17 +421,26 @@ class Session:
 
     def load_device(self, d_buf=None, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
-        all been queued -- load() queues them behind the PCIe copies).  --bin-qual first; then the line count alone (--fingerprint, --qc),
+        all been queued -- load() queues them behind the PCIe copies).  --trim, --filter, --bin-qual first, in that order; then the line count alone (--fingerprint, --qc),
         or the queued step bench.py times, or -- where that does not hold for this file -- the same two reads with the record index,
         or -- where that has no kernel either, and under --multi-pass -- the plain statistics pass.  Same results whichever path."""
         self._reset_load_state()
         if d_buf is not None: self.d_buf = d_buf         # (the loaders of this class leave the text in `d_buf` and pass none: --filter can then free it)
         del d_buf
+        if self.args.trim is not None:
+            self.trim_records(census)
+            census = None                                # (the trimmed reads in a buffer of their own; the census of the untrimmed text has been closed)
         if self.args.filter is not None:
             self.filter_records(census)
             census = None                                # (the kept reads in a buffer of their own; the census of the unfiltered text has been closed)
+        trimmed = None
+        if self._pre_index is not None:                  # --trim without --filter: the index uq_trim_records wrote is the trimmed text's
+            (n, ls), self._pre_index = self._pre_index, None
+            trimmed = (4 * n, ls)
+            del ls
         d_buf = self.d_buf
-        binned = self.bin_qualities(census) if self.args.bin_qual is not None else None      # (line count, record index)
+        binned = self.bin_qualities(census) if self.args.bin_qual is not None else trimmed      # (line count, record index)
+        del trimmed
         if binned is not None: census = None             # (its census has been closed; the step below runs its own: one more census per encode, with the flag only)
         if self.index_only: return self._load_index_only(census, binned)
         if binned is not None: self._d_ls = binned[1]
@@ -536,6 +557,36 @@ class Session:
             nk, ls_k = self.indexed(d_out, None)
             self.require_mates(d_out, ls_k, 0, 2, d_out, ls_k, 1, 2, nk // 2)
 
+    def trim_records(self, census=None):
+        """--trim, at the head of load_device, in front of filter_records and bin_qualities (the filter judges the reads as trimmed; the
+        qualities are judged as given): the records of self.d_buf get their windows (uq_trim_mark) and their places (uq_trim_plan) and are
+        copied, cut, back to back into a new buffer (uq_trim_records), which replaces self.d_buf; the old one is freed, by the rules
+        filter_records states.  Needs the record index (the census, closed here if load() had begun one, + uq_index_lines -- or what a
+        paired loader left in `_pre_index`); the index of the trimmed text, which the copy writes, is handed on in `_pre_index`: --filter
+        takes it and censuses nothing.  Reads left without bases are a refusal before anything is written, unless --filter drops them."""
+        ops, ctx, args = self.ops, self.ctx, self.args
+        d_buf = self.d_buf
+        steps, explicit = trim_steps(args.trim)
+        if self._pre_index is not None: (n, ls), self._pre_index = self._pre_index, None
+        else:
+            nlines = census.end() if census is not None else (ops.count_lines(ctx, d_buf) if d_buf.numel() else 0)
+            if census is not None: census.buf = None     # (closed: it lets go of the untrimmed text)
+            n = whole_records(nlines)
+            ls = ops.index_lines(ctx, d_buf, nlines)
+        d_report = ops.trim_report_new(ctx)
+        window = ops.trim_mark(ctx, d_report, d_buf, ls, 0, n, ops.trim_params(**steps))
+        dst, size = ops.trim_plan(ctx, ls, 0, n, window)
+        report = ops.trim_report_fetch(ctx, d_report)
+        if report['emptied'] and not (args.filter is not None and filter_criteria(args.filter)[0]['min_len'] >= 1):
+            error('ERROR: --trim %s leaves %d reads without bases; add --filter min-len=1 (or higher)' % (args.trim, report['emptied']))
+        d_out, ls_out = ops.trim_records(ctx, d_buf, ls, 0, n, window, dst, out_bytes=size, index=True)
+        ctx.sync()
+        self.d_buf = d_out
+        del d_buf, window, dst, ls                      # the untrimmed text is freed here (see filter_records)
+        self.path, self._host = None, None              # no file holds the trimmed bytes: the host copy (`host`) comes from d_buf
+        self.trimming = {'spec': args.trim, 'criteria': explicit, 'report': report}
+        self._pre_index = (n, ls_out)
+
     def bin_qualities(self, census=None):
         """--bin-qual, at the head of load_device: the table of the spec applied to every quality line of self.d_buf, in place
         (uq_requantise_qualities), before the head guess, the statistics, the pack or a fingerprint see the text -- every path works on the
@@ -649,6 +700,9 @@ class Session:
             binning = {'spec': args.bin_qual, 'ranges': self.bin_qual_ranges or bin_qual_table(args.bin_qual)[1],
                        'changed': self.binned_changed_in_file()}
             self.say('Binned qualities (%s): %d of %d quality characters changed' % (args.bin_qual, binning['changed'], sum(d['qual_distribution'].values())))
+        if self.trimming is not None:
+            from . import rectrim
+            self.say(rectrim.report_line(self.trimming['report']))
         if self.filtering is not None:
             from . import recfilter
             self.say(recfilter.report_line(self.filtering['report']))
@@ -661,6 +715,7 @@ class Session:
             'QNAME_prefix': prefix, 'QNAME_suffix': suffix, 'QNAME_separators': separators, 'QNAME_columns': columns,
         }
         if binning is not None: self.config['quality_binning'] = binning
+        if self.trimming is not None: self.config['trim'] = dict(self.trimming)
         if self.filtering is not None: self.config['filter'] = dict(self.filtering)
         if self.pairing is not None: self.config['paired'] = dict(self.pairing)
 
@@ -1118,6 +1173,9 @@ class Session:
                 key + ' fingerprint equal', hx(got['records']))
             if want['plus_text']: line += '; the text after the + of %d third lines is not kept by the format' % want['plus_text']
             if self.pairing is not None: line += '; %d pairs, mates interleaved' % self.pairing['pairs']
+            if self.trimming is not None:                     # `want` was taken from the trimmed text in HBM
+                line += '; gives back the reads as --trim %s cut them, %d of %d bases' % (
+                    self.trimming['criteria'], self.trimming['report']['bases_out'], self.trimming['report']['bases_in'])
             if self.filtering is not None:                    # `want` was taken from the filtered text in HBM
                 line += '; gives back the %d reads --filter kept of %d' % (self.filtering['report']['reads_out'], self.filtering['report']['reads_in'])
             if args.bin_qual is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
