@@ -7,6 +7,8 @@ script reports the patterns that cost round 4 its easy milliseconds:
          pointers read out of a struct) -- counted in lgkmcnt as well and returning out of order, every later wait becomes a full one
   sload  scalar loads inside a loop (followed by an immediate wait when the kernel is short of SGPRs)
   spill  v_readlane / v_writelane (SGPR spills) inside loops, scratch accesses, VGPR / SGPR counts
+  wds    ds_write_b16 / b32 / b64 or ds_read_b64 inside a loop with an ODD immediate offset: byte accesses that the compiler merged into a wide one at
+         an address the source never aligned (unaligned LDS accesses take the lanes one by one: DESIGN 9, 29)
     python tools/isa_scan.py [file.hip ...] [--all] [--pattern NAME]     (default: kernels with any finding; --pattern prints the L/W/S/B string of kernels matching NAME)"""
 import glob, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -38,7 +40,7 @@ def scan(path, want_all, pattern):
     for i in range(1, len(parts), 2):
         name, body = parts[i], parts[i + 1].split('.Lfunc_end')[0]
         if name not in meta: continue
-        depth, seq, flat_loop, sload_loop, spill_loop = 0, [], 0, 0, 0
+        depth, seq, flat_loop, sload_loop, spill_loop, wds = 0, [], 0, 0, 0, 0
         for l in body.split('\n'):
             m = re.search(r'Depth=(\d)', l)
             if l.startswith('.LBB') or l.startswith('; %bb'): depth = int(m.group(1)) if m else 0
@@ -47,6 +49,7 @@ def scan(path, want_all, pattern):
             if depth and re.search(r'\bflat_(load|store)', l): flat_loop += 1
             if depth and re.search(r'\bs_(buffer_)?load_dword', l): sload_loop += 1
             if depth and re.search(r'v_(read|write)lane_b32', l): spill_loop += 1
+            if depth and re.search(r'\b(ds_write_b(16|32|64)|ds_read_b64)\b.*\boffset:\d*[13579]\b', l): wds += 1
         seq = ''.join(seq)
         lwl = len(re.findall(r'[LF]W(?=[LF])', seq)); sws = len(re.findall(r'SW(?=S)', seq))
         short = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip().replace('(anonymous namespace)::', '').replace('void ', '', 1).split('(')[0]
@@ -54,9 +57,9 @@ def scan(path, want_all, pattern):
             if pattern in short: print('%s\n    %s' % (short, seq))
             continue
         v, sg, vs, scr = meta[name]
-        if want_all or lwl >= 2 or sws >= 2 or flat_loop or sload_loop or vs or scr:
-            rows.append('%-12s %-64s lwl %3d  sws %3d  flat-in-loop %2d  sload-in-loop %2d  sgpr-spill-ops-in-loops %3d  vgpr %3d sgpr %3d vgpr-spills %d scratch %d'
-                        % (os.path.basename(path)[:-2], short[:64], lwl, sws, flat_loop, sload_loop, spill_loop, v, sg, vs, scr))
+        if want_all or lwl >= 2 or sws >= 2 or flat_loop or sload_loop or vs or scr or wds:
+            rows.append('%-12s %-64s lwl %3d  sws %3d  flat-in-loop %2d  sload-in-loop %2d  sgpr-spill-ops-in-loops %3d  vgpr %3d sgpr %3d vgpr-spills %d scratch %d  wds %2d'
+                        % (os.path.basename(path)[:-2], short[:64], lwl, sws, flat_loop, sload_loop, spill_loop, v, sg, vs, scr, wds))
     return rows
 
 def main():

@@ -108,6 +108,17 @@ __device__ __forceinline__ uint32_t group_byte(uint32_t a0, uint32_t a1, int i) 
 #endif
     return (uint32_t)((((uint64_t)a0 << (4 * B)) | a1) >> (8 * i));
 }
+// One byte into the LDS image of a row, as ONE ds_write_b8.  (Plain byte stores of a group's bytes are merged by the compiler into a v_perm_b32 and a
+// ds_write_b32 at `row end - 4`: an address that is dword-aligned for one lane in four, where the store takes the lanes one by one -- DESIGN 29.  A
+// volatile store through an LDS-qualified pointer stays a byte store, keeps the d16_hi forms and draws no wait behind it; through a generic pointer it
+// would be a flat store.)
+__device__ __forceinline__ void lds_store8(uint8_t* p, uint32_t v) {
+#ifdef PK_MERGED_STORES
+    *p = (uint8_t)v;
+#else
+    *(volatile __attribute__((address_space(3))) uint8_t*)p = (uint8_t)v;
+#endif
+}
 
 // LDS tile (16-byte aligned) -> global span, with the widest stores the destination alignment allows.
 // CLEAR: every byte is zeroed right after the lane has read it (the variable-length dealing leaves the empty upper parts of the rows to that).
@@ -567,6 +578,30 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         if (ok) {
             // ---- B: P lanes per read; a lane owns groups of 8 consecutive symbols, both streams:
             //         characters -> codes -> bits (8 symbols of b bits = b whole bytes)
+            // the eight (base code, quality code) pairs of a group onto the count table (STATS)
+            auto count_pairs =[&](const uint32_t c0, const uint32_t c1, const uint32_t x0, const uint32_t x1) {
+                uint8_t* hb = (uint8_t*)cnt_tab + ((lane_id() & (PKS_COPIES - 1)) << 2);
+                if constexpr (BD == 2) {
+                    const uint32_t bin0 = (c0 << 6) | x0, bin1 = (c1 << 6) | x1;    // BQ <= 6 and two bits of base: a bin per byte
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if constexpr (PKS_COPIES == 1) {
+                            atomicAdd(&cnt_tab[(bin0 >> (8 * k)) & 0xFFu], 1u);
+                            atomicAdd(&cnt_tab[(bin1 >> (8 * k)) & 0xFFu], 1u);
+                        } else {
+                            atomicAdd((uint32_t*)(hb + (((bin0 >> (8 * k)) & 0xFFu) * (4 * PKS_COPIES))), 1u);
+                            atomicAdd((uint32_t*)(hb + (((bin1 >> (8 * k)) & 0xFFu) * (4 * PKS_COPIES))), 1u);
+                        }
+                    }
+                } else {                                                            // three bits of base: nine bits of bin, pair by pair
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t b0 = (((c0 >> (8 * k)) & 7u) << 6) | ((x0 >> (8 * k)) & 63u), b1 = (((c1 >> (8 * k)) & 7u) << 6) | ((x1 >> (8 * k)) & 63u);
+                        atomicAdd((uint32_t*)(hb + b0 * (4 * PKS_COPIES)), 1u);
+                        atomicAdd((uint32_t*)(hb + b1 * (4 * PKS_COPIES)), 1u);
+                    }
+                }
+            };
             // one group of eight symbols of read r (length L, SEQ / QUAL lines at so / qo of the stage, the rows' last bytes at orow_d / orow_q):
             // characters -> codes -> bits, counted (STATS), stored into the LDS image of the two tables
             // (wd / wq: the dword-aligned LDS offsets of the group's two windows, shd / shq: the windows' byte phases -- the same for every group of a
@@ -621,27 +656,7 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
 #else
                         else {
 #endif
-                            uint8_t* hb = (uint8_t*)cnt_tab + ((lane_id() & (PKS_COPIES - 1)) << 2);
-                            if constexpr (BD == 2) {
-                                const uint32_t bin0 = (c0 << 6) | x0, bin1 = (c1 << 6) | x1;    // BQ <= 6 and two bits of base: a bin per byte
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) {
-                                    if constexpr (PKS_COPIES == 1) {
-                                        atomicAdd(&cnt_tab[(bin0 >> (8 * k)) & 0xFFu], 1u);
-                                        atomicAdd(&cnt_tab[(bin1 >> (8 * k)) & 0xFFu], 1u);
-                                    } else {
-                                        atomicAdd((uint32_t*)(hb + (((bin0 >> (8 * k)) & 0xFFu) * (4 * PKS_COPIES))), 1u);
-                                        atomicAdd((uint32_t*)(hb + (((bin1 >> (8 * k)) & 0xFFu) * (4 * PKS_COPIES))), 1u);
-                                    }
-                                }
-                            } else {                                                            // three bits of base: nine bits of bin, pair by pair
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) {
-                                    const uint32_t b0 = (((c0 >> (8 * k)) & 7u) << 6) | ((x0 >> (8 * k)) & 63u), b1 = (((c1 >> (8 * k)) & 7u) << 6) | ((x1 >> (8 * k)) & 63u);
-                                    atomicAdd((uint32_t*)(hb + b0 * (4 * PKS_COPIES)), 1u);
-                                    atomicAdd((uint32_t*)(hb + b1 * (4 * PKS_COPIES)), 1u);
-                                }
-                            }
+                            count_pairs(c0, c1, x0, x1);
                             if (j0 < 0) fill_pairs += (uint32_t)(-j0);
                             if (NTRICK && (e0 | e1)) {
                                 // the N-trick base's own pairs: the guess says it occurs with ONE quality character (that is what
@@ -693,19 +708,19 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                 else if (false)
 #endif
                 if (gg + 1 < g.G) {
-                    // byte stores: unaligned ds_write_b32 / b16 pieces are accepted by gfx950 but slower (1.11 -> 1.27 ms)
+                    // byte stores: unaligned ds_write_b32 / b16 pieces are accepted by gfx950 but slower (1.11 -> 1.27 ms); lds_store8 keeps them bytes
 #pragma unroll
-                    for (int i = 0; i < BD; ++i) od[-i] = (uint8_t)group_byte<BD>(ad0, ad1, i);
+                    for (int i = 0; i < BD; ++i) lds_store8(od - i, group_byte<BD>(ad0, ad1, i));
 #pragma unroll
-                    for (int i = 0; i < BQ; ++i) oq[-i] = (uint8_t)group_byte<BQ>(aq0, aq1, i);
+                    for (int i = 0; i < BQ; ++i) lds_store8(oq - i, group_byte<BQ>(aq0, aq1, i));
                 } else {
                     const uint32_t nd = g.Cd - BD * gg, nq = g.Cq - BQ * gg;     // bytes left in the row from here up
 #pragma unroll
                     for (int i = 0; i < BD; ++i)
-                        if ((uint32_t)i < nd) od[-i] = (uint8_t)group_byte<BD>(ad0, ad1, i);
+                        if ((uint32_t)i < nd) lds_store8(od - i, group_byte<BD>(ad0, ad1, i));
 #pragma unroll
                     for (int i = 0; i < BQ; ++i)
-                        if ((uint32_t)i < nq) oq[-i] = (uint8_t)group_byte<BQ>(aq0, aq1, i);
+                        if ((uint32_t)i < nq) lds_store8(oq - i, group_byte<BQ>(aq0, aq1, i));
                 }
             };
             if (rr < Rt) {
@@ -731,7 +746,65 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                 const uint32_t shd = (uint32_t)wd & 3u, shq = (uint32_t)wq & 3u;
                 wd &= ~3; wq &= ~3;
                 const int32_t wstep = 8 * (int32_t)g.P;
-                for (uint32_t gg = pp; gg < gend; gg += g.P, wd -= wstep, wq -= wstep) pack_group(r, L, wd, shd, wq, shq, orow_d, orow_q, gg);
+                uint32_t gg = pp;
+#if !defined(PK_NO_STRAIGHT) && !defined(PK_ABL_NOSTORE)
+                if constexpr (FAST) {
+                    // The lane's FULL groups (8 gg + 8 <= L: no fill, no sentinel, and the row holds all their bytes, since L <= dna_max) in a body
+                    // without exec-mask regions: pack_group's seven divergent `if`s are all false for them.  A symbol outside the guess in ANY lane
+                    // of the wave ends the loop for the whole wave -- one uniform branch -- and pack_group takes the lane's groups from there on.
+                    const uint32_t gfull = L >> 3;
+                    for (; gg < gfull; gg += g.P, wd -= wstep, wq -= wstep) {
+                        uint32_t b_lo, b_hi, q_lo, q_hi;
+                        lds_window8_at(stage, wd, shd, b_lo, b_hi);
+                        lds_window8_at(stage, wq, shq, q_lo, q_hi);
+                        uint32_t c0, c1, e0, e1;
+                        if constexpr (BD == 2) {
+                            c0 = acgt_codes(b_lo); c1 = acgt_codes(b_hi);
+                            e0 = acgt_chars(c0) ^ b_lo; e1 = acgt_chars(c1) ^ b_hi;
+                        } else {
+                            c0 = __builtin_amdgcn_perm(g.i2c_hi, g.i2c_lo, (b_lo >> g.h_shift) & 0x07070707u);
+                            c1 = __builtin_amdgcn_perm(g.i2c_hi, g.i2c_lo, (b_hi >> g.h_shift) & 0x07070707u);
+                            e0 = __builtin_amdgcn_perm(g.c2c_hi, g.c2c_lo, c0) ^ b_lo; e1 = __builtin_amdgcn_perm(g.c2c_hi, g.c2c_lo, c1) ^ b_hi;
+                        }
+                        const uint32_t u0 = q_lo + g.q_addlo, u1 = q_hi + g.q_addlo;
+                        uint32_t bq0 = (q_lo | (q_lo + g.q_addhi) | ~u0) & 0x80808080u, bq1 = (q_hi | (q_hi + g.q_addhi) | ~u1) & 0x80808080u;
+                        uint32_t x0 = u0 & 0x7F7F7F7Fu, x1 = u1 & 0x7F7F7F7Fu;
+                        uint32_t err = e0 | e1, n_here = 0, n_other_q = 0;
+                        if constexpr (NTRICK) {
+                            if (__builtin_amdgcn_ballot_w64(err != 0)) {       // (uniform: the N-trick base somewhere in the wave's 512 symbols)
+                                // pack_group's N handling, bitwise for every lane (a quality byte beyond 127 is an error there with or without an N)
+                                const uint32_t m0 = nonzero_bytes(e0), m1 = nonzero_bytes(e1);
+                                err = ((b_lo ^ g.n_char) & m0) | ((b_hi ^ g.n_char) & m1) | ((q_lo | q_hi) & 0x80808080u);
+                                c0 &= ~m0; c1 &= ~m1;
+                                x0 = bfi(m0, g.n_code, x0); x1 = bfi(m1, g.n_code, x1);
+                                bq0 &= ~m0; bq1 &= ~m1;
+                                if constexpr (STATS) {
+                                    n_here = (uint32_t)__popc(m0 & 0x01010101u) + (uint32_t)__popc(m1 & 0x01010101u);
+                                    n_other_q = (m0 & nonzero_bytes(q_lo ^ g.n_qchar)) | (m1 & nonzero_bytes(q_hi ^ g.n_qchar));
+                                }
+                            }
+                        }
+                        if (__builtin_amdgcn_ballot_w64((err | bq0 | bq1) != 0)) break;
+                        const uint32_t ad0 = pack4<BD>(c0), ad1 = pack4<BD>(c1), aq0 = pack4<BQ>(x0), aq1 = pack4<BQ>(x1);
+                        if constexpr (STATS) {
+#ifndef PK_ABL_NOCOUNT
+                            count_pairs(c0, c1, x0, x1);
+#endif
+                            if constexpr (NTRICK) {                            // (the N-trick base's own pairs: see pack_group)
+                                n_pairs += n_here;
+                                if (n_other_q) incomplete = true;
+                            }
+                        }
+                        uint8_t* od = orow_d - BD * gg;
+                        uint8_t* oq = orow_q - BQ * gg;
+#pragma unroll
+                        for (int i = 0; i < BD; ++i) lds_store8(od - i, group_byte<BD>(ad0, ad1, i));
+#pragma unroll
+                        for (int i = 0; i < BQ; ++i) lds_store8(oq - i, group_byte<BQ>(aq0, aq1, i));
+                    }
+                }
+#endif
+                for (; gg < gend; gg += g.P, wd -= wstep, wq -= wstep) pack_group(r, L, wd, shd, wq, shq, orow_d, orow_q, gg);
 #endif
             }
         }
