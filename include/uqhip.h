@@ -316,6 +316,41 @@ int uq_trim_records(uq_ctx* ctx, const uint8_t* d_buf, uint64_t nbytes, const ui
 int uq_trim_records_host(const uint8_t* h_buf, uint64_t nbytes, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
                          const uint32_t* h_window, const uint64_t* h_dst, uint8_t* h_out, uint64_t out_capacity, uint64_t* h_line_start_out);
 
+/* ---- 3' adapter removal (`--adapter`; an extension).  A marking step that NARROWS the windows of the trim section above:
+ * the plan and the copy are uq_trim_plan and uq_trim_records.  cls is the QC tables' class (uqqc1, above): A 0, C 1, G 2, T 3 in either case,
+ * N 4, anything else 5.  An ADAPTER A is La letters of ACGT, 1 <= La <= UQ_ADAPTER_MAX, stored as classes 0 .. 3 (lower case is folded by whoever
+ * fills the structure: the library sees classes only).  A record comes with a window [a, b), a <= b <= Ls: the one uq_trim_mark wrote, or
+ * (0, Ls) when UQ_ADAPTER_FRESH is set -- then d_window is not read, only written.  A record with Ls != Lu keeps (0, Ls) and counts once in
+ * len_mismatch and in reads_in, with Ls added to bases_in and to bases_out.  For every other record and every p in [a, b):
+ *   m(p) = min(La, b - p);
+ *   p is a CANDIDATE when m(p) >= overlap and #{ j < m(p) : cls(s[p + j]) != A[j] } <= (m(p) * err_pct) / 100 (integer division); N and
+ *   other bytes in the read never match (a '\r' in front of the '\n' is the line's last byte, class 5: a mismatch like any other).
+ * The new window is [a, p*) for the LEFTMOST candidate p* (the rule fastp uses); it is unchanged when there is none.  The match is FULL when
+ * m(p*) == La, otherwise PARTIAL; p* == a (with a < b) EMPTIES the read: an adapter dimer.  With UQ_ADAPTER_PAIRED the records with odd
+ * first_read + i are matched against seq2, the others against seq1 (the interleaved layout of the pairs section); without it every record
+ * uses seq1 and len2 / seq2 only have to be well-formed.  Hamming distance only: no insertions or deletions.
+ * uq_adapter_report (device, 8-byte aligned; uq_adapter_report_init zeroes it): nine sums, so calls and shards add.  bases_in = SUM b - a as
+ *   received, bases_out = the same sum afterwards, reads_cut = full + partial, mate2 = the cut records that used seq2, emptied = the windows
+ *   that were not empty and are now.
+ * uq_adapter_mark reads the records, their line starts and (without FRESH) d_window, writes d_window[2 i], d_window[2 i + 1] for every record
+ *   first_read + i, i < nreads, and ADDS every field of the report, nothing else; queued on the context's stream, nothing read back.
+ * Errors: null arguments, d_window not 4-byte or d_report not 8-byte aligned, len1 outside 1 .. 64, len2 > 64 (or 0 with PAIRED), a sequence
+ * byte above 3, overlap outside 1 .. min(len1, len2 where PAIRED), err_pct > 30, unknown flag bits, non-zero reserved words.  A window with
+ * a > b or b > Ls handed in is an error in the _host form and UNDEFINED on the device (uq_trim_plan's contract).  An error of either form
+ * is raised before anything is written: windows and report are as they were.  Any buffer alignment; lines
+ * shorter than 2^32 bytes with their '\n'.  The _host forms: the same, sequentially, on host memory (need no GPU). */
+#define UQ_ADAPTER_MAX    64
+#define UQ_ADAPTER_FRESH  1u
+#define UQ_ADAPTER_PAIRED 2u
+typedef struct uq_adapter_params { uint32_t len1, len2, overlap, err_pct, flags, reserved[3]; uint8_t seq1[64], seq2[64]; } uq_adapter_params;
+typedef struct uq_adapter_report { uint64_t reads_in, bases_in, bases_out, reads_cut, full, partial, mate2, emptied, len_mismatch; } uq_adapter_report;
+int uq_adapter_report_init(uq_ctx* ctx, uq_adapter_report* d_report);
+int uq_adapter_report_init_host(uq_adapter_report* h_report);
+int uq_adapter_mark(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                    const uq_adapter_params* h_params, uint32_t* d_window, uq_adapter_report* d_report);
+int uq_adapter_mark_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                         const uq_adapter_params* h_params, uint32_t* h_window, uq_adapter_report* h_report);
+
 /* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

@@ -120,6 +120,15 @@ class TrimReport(C.Structure):
                                           'cut_fixed', 'cut_polyg', 'cut_q5', 'cut_q3', 'cut_n', 'emptied', 'len_mismatch')]
 
 
+class AdapterParams(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ('len1', 'len2', 'overlap', 'err_pct', 'flags')] + [('reserved', C.c_uint32 * 3),
+                                                                                             ('seq1', C.c_uint8 * 64), ('seq2', C.c_uint8 * 64)]
+
+
+class AdapterReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('reads_in', 'bases_in', 'bases_out', 'reads_cut', 'full', 'partial', 'mate2', 'emptied', 'len_mismatch')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -188,6 +197,10 @@ SIGNATURES = {
     'uq_trim_plan_host': [_vp, _u64, _u64, _vp, _vp, _P(_u64)],
     'uq_trim_records': [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
     'uq_trim_records_host': [_vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp],
+    'uq_adapter_report_init': [_vp, _vp],
+    'uq_adapter_report_init_host': [_P(AdapterReport)],
+    'uq_adapter_mark': [_vp, _vp, _vp, _u64, _u64, _P(AdapterParams), _vp, _vp],
+    'uq_adapter_mark_host': [_vp, _vp, _u64, _u64, _P(AdapterParams), _vp, _P(AdapterReport)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

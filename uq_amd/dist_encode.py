@@ -445,6 +445,9 @@ def main(argv=None):
     if args.trim is not None:
         print('ERROR: --trim is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder does not trim the reads of its shards yet')
         return 1
+    if args.adapter is not None:
+        print('ERROR: --adapter is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder does not cut the reads of its shards yet')
+        return 1
     if args.verify or args.fingerprint:
         print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
               "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, AdapterParams, AdapterReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -662,6 +662,75 @@ def trim_records_host(data, line_start, window, dst, first_read=0, out_capacity=
          C.c_void_p(window.ctypes.data if nreads else 0), C.c_void_p(dst.ctypes.data), C.c_void_p(out.ctypes.data if out.size else 0),
          size if out_capacity is None else int(out_capacity), C.c_void_p(lso.ctypes.data) if index else C.c_void_p(0))
     return (out, lso) if index else out
+
+
+# ------------------------------------------------------------------ 3' adapters (include/uqhip.h)
+ADAPTER_REPORT_FIELDS = tuple(k for k, _ in AdapterReport._fields_)
+ADAPTER_MAX = 64
+ADAPTER_FRESH = 1
+ADAPTER_PAIRED = 2
+_ADAPTER_CLASS = {'A': 0, 'C': 1, 'G': 2, 'T': 3}
+
+
+def _adapter_classes(seq, what):
+    """A sequence as the library takes it: classes 0..3.  Letters of either case, or integers handed through as they are (the tests' way to
+    reach the library's own checks)."""
+    if isinstance(seq, str):
+        try: return [_ADAPTER_CLASS[c] for c in seq.upper()]
+        except KeyError: raise ValueError('adapter: %s %r holds letters other than A, C, G, T' % (what, seq))
+    return [int(c) for c in seq]
+
+
+def adapter_params(seq, seq2=None, err=10, overlap=3, flags=0, len1=None, len2=None, reserved=(0, 0, 0)):
+    """A uq_adapter_params.  seq / seq2: letters or classes (at most 64 are stored); len1 / len2 override the lengths."""
+    p = AdapterParams()
+    for name, s, n in (('seq1', seq, len1), ('seq2', seq2, len2)):
+        cls = _adapter_classes(s, name) if s is not None else []
+        for j, c in enumerate(cls[:ADAPTER_MAX]): getattr(p, name)[j] = c
+        setattr(p, 'len1' if name == 'seq1' else 'len2', len(cls) if n is None else int(n))
+    p.overlap, p.err_pct, p.flags = int(overlap), int(err), int(flags)
+    for j in range(3): p.reserved[j] = int(reserved[j])
+    return p
+
+
+def adapter_report_new(ctx):
+    """A zeroed device uq_adapter_report (int64[9])."""
+    t = ctx.torch
+    d = t.empty(len(ADAPTER_REPORT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_adapter_report_init', ctx.h, _p(d))
+    return d
+
+
+def adapter_report_fetch(ctx, d_report):
+    """The device report as a dict of Python integers (synchronises)."""
+    return dict(zip(ADAPTER_REPORT_FIELDS, (int(v) for v in ctx.to_numpy(d_report).view(np.uint64))))
+
+
+def adapter_mark(ctx, d_report, buf, line_start, first_read, nreads, params, window=None):
+    """Narrows the windows of the records [first_read, first_read + nreads) of buf to the leftmost adapter candidate (`window`: the int32
+    tensor uq_trim_mark filled; None: a new one, which needs ADAPTER_FRESH in params.flags), the counts added into d_report (queued)."""
+    t = ctx.torch
+    if window is None:
+        if not params.flags & ADAPTER_FRESH: raise ValueError('adapter: no windows given and ADAPTER_FRESH is not set')
+        window = t.empty(2 * nreads, dtype=t.int32, device=ctx.device)
+    call('uq_adapter_mark', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), C.byref(params), _p(window), _p(d_report))
+    return window
+
+
+def adapter_mark_host(data, params, line_start=None, first_read=0, nreads=None, window=None, report=None):
+    """uq_adapter_mark_host: the same on the CPU over host bytes (needs no GPU) -> (uint32[nreads, 2] windows, report dict).  `window`: the
+    windows to narrow (copied; not needed with ADAPTER_FRESH); `report`: an earlier one to add to."""
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'adapter')
+    r = AdapterReport(*[report[k] for k in ADAPTER_REPORT_FIELDS]) if report is not None else AdapterReport()
+    if window is None:
+        if not params.flags & ADAPTER_FRESH: raise ValueError('adapter: no windows given and ADAPTER_FRESH is not set')
+        window = np.zeros((nreads, 2), dtype=np.uint32)
+    else:
+        window = np.array(window, dtype=np.uint32).reshape(-1, 2)
+        if len(window) != nreads: raise ValueError('adapter: %d windows for %d records' % (len(window), nreads))
+    call('uq_adapter_mark_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads),
+         C.byref(params), C.c_void_p(window.ctypes.data if nreads else 0), C.byref(r))
+    return window, {k: int(getattr(r, k)) for k in ADAPTER_REPORT_FIELDS}
 
 
 # ------------------------------------------------------------------ pack

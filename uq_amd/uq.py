@@ -103,6 +103,8 @@ def build_parser():
     p.add_argument('--filter', action='store', default=None, metavar='SPEC', help=recfilter.HELP)
     from . import rectrim
     p.add_argument('--trim', action='store', default=None, metavar='SPEC', help=rectrim.HELP)
+    from . import adapters
+    p.add_argument('--adapter', action='store', default=None, metavar='SPEC', help=adapters.HELP)
     p.add_argument('--mate2', action='store', default=None, metavar='R2.fastq',
                    help='paired-end input: -i is R1, this is R2 (plain, BGZF or other gzip, each by its content).  The read counts must be equal and '
                         'read r of R2 must be the mate of read r of R1 (same QNAME up to the first space or tab, /1 with /2 allowed); the two '
@@ -169,6 +171,10 @@ def validate_args(args):
     if args.trim is not None:
         if args.decode: error('ERROR: --trim cuts reads before an encode stores them: the text --decode writes is what the container holds')
         trim_steps(args.trim)
+    if args.adapter is not None:
+        if args.decode: error('ERROR: --adapter cuts reads before an encode stores them: the text --decode writes is what the container holds')
+        if adapter_criteria(args.adapter)[0]['seq2'] is not None and args.mate2 is None and not args.interleaved:
+            error('ERROR: --adapter %s: seq2 is the second mates\' adapter: use it together with --mate2 or --interleaved' % args.adapter)
     mate2, interleaved, split = args.mate2, args.interleaved, args.split_mates
     if mate2 is not None and interleaved:
         error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
@@ -202,6 +208,12 @@ def trim_steps(spec):
     """--trim SPEC -> (the steps of uq_trim_params, the explicit form of the spec); a bad spec is a UqError."""
     from . import rectrim
     return rectrim.parse(spec), rectrim.explicit(spec)
+
+
+def adapter_criteria(spec):
+    """--adapter SPEC -> (seq, seq2, err, overlap as adapters.parse gives them, the explicit form of the spec); a bad spec is a UqError."""
+    from . import adapters
+    return adapters.parse(spec), adapters.explicit(spec)
 
 
 def npy_header(shape, fortran_order, dtype):
@@ -253,6 +265,7 @@ class Session:
         self.binned_changed = 0    # --bin-qual: quality characters this session's binning changed
         self.filtering = None      # --filter: config.json's "filter" value (spec, criteria, unit, report)
         self.trimming = None       # --trim: config.json's "trim" value (spec, criteria, report)
+        self.adapting = None       # --adapter: config.json's "adapter" value (spec, criteria, report)
         self._pre_index = None     # --trim, --filter: (reads, record index) of the buffer a paired loader or trim_records hands on, until the next step of load_device takes it
         self.d_buf = None          # the FASTQ text in HBM (uint8 device tensor)
         self.total = 0             # reads in d_buf
@@ -427,7 +440,7 @@ class Session:
         self._reset_load_state()
         if d_buf is not None: self.d_buf = d_buf         # (the loaders of this class leave the text in `d_buf` and pass none: --filter can then free it)
         del d_buf
-        if self.args.trim is not None:
+        if self.args.trim is not None or self.args.adapter is not None:
             self.trim_records(census)
             census = None                                # (the trimmed reads in a buffer of their own; the census of the untrimmed text has been closed)
         if self.args.filter is not None:
@@ -558,33 +571,49 @@ class Session:
             self.require_mates(d_out, ls_k, 0, 2, d_out, ls_k, 1, 2, nk // 2)
 
     def trim_records(self, census=None):
-        """--trim, at the head of load_device, in front of filter_records and bin_qualities (the filter judges the reads as trimmed; the
-        qualities are judged as given): the records of self.d_buf get their windows (uq_trim_mark) and their places (uq_trim_plan) and are
+        """--trim and --adapter, at the head of load_device, in front of filter_records and bin_qualities (the filter judges the reads as trimmed; the
+        qualities are judged as given): the records of self.d_buf get their windows (uq_trim_mark under --trim; narrowed by uq_adapter_mark
+        under --adapter, which starts from whole lines when there is no --trim) and their places (uq_trim_plan) and are
         copied, cut, back to back into a new buffer (uq_trim_records), which replaces self.d_buf; the old one is freed, by the rules
         filter_records states.  Needs the record index (the census, closed here if load() had begun one, + uq_index_lines -- or what a
         paired loader left in `_pre_index`); the index of the trimmed text, which the copy writes, is handed on in `_pre_index`: --filter
         takes it and censuses nothing.  Reads left without bases are a refusal before anything is written, unless --filter drops them."""
         ops, ctx, args = self.ops, self.ctx, self.args
         d_buf = self.d_buf
-        steps, explicit = trim_steps(args.trim)
+        adapter = args.adapter
+        if args.trim is not None: steps, explicit = trim_steps(args.trim)
+        if adapter is not None: a_criteria, a_explicit = adapter_criteria(adapter)
         if self._pre_index is not None: (n, ls), self._pre_index = self._pre_index, None
         else:
             nlines = census.end() if census is not None else (ops.count_lines(ctx, d_buf) if d_buf.numel() else 0)
             if census is not None: census.buf = None     # (closed: it lets go of the untrimmed text)
             n = whole_records(nlines)
             ls = ops.index_lines(ctx, d_buf, nlines)
-        d_report = ops.trim_report_new(ctx)
-        window = ops.trim_mark(ctx, d_report, d_buf, ls, 0, n, ops.trim_params(**steps))
+        window, report, a_report = None, None, None
+        if args.trim is not None:
+            d_report = ops.trim_report_new(ctx)
+            window = ops.trim_mark(ctx, d_report, d_buf, ls, 0, n, ops.trim_params(**steps))
+        if adapter is not None:                         # behind the trimmer's four steps: it narrows their windows (a poly-G tail no longer hides the adapter in front of it)
+            paired = args.mate2 is not None or args.interleaved
+            flags = (ops.ADAPTER_FRESH if window is None else 0) | (ops.ADAPTER_PAIRED if paired else 0)
+            d_areport = ops.adapter_report_new(ctx)
+            window = ops.adapter_mark(ctx, d_areport, d_buf, ls, 0, n, ops.adapter_params(
+                a_criteria['seq'], (a_criteria['seq2'] or a_criteria['seq']) if paired else None, a_criteria['err'], a_criteria['overlap'], flags), window)
         dst, size = ops.trim_plan(ctx, ls, 0, n, window)
-        report = ops.trim_report_fetch(ctx, d_report)
-        if report['emptied'] and not (args.filter is not None and filter_criteria(args.filter)[0]['min_len'] >= 1):
+        if args.trim is not None: report = ops.trim_report_fetch(ctx, d_report)
+        if adapter is not None: a_report = ops.adapter_report_fetch(ctx, d_areport)
+        keeps_bases = args.filter is not None and filter_criteria(args.filter)[0]['min_len'] >= 1
+        if report is not None and report['emptied'] and not keeps_bases:
             error('ERROR: --trim %s leaves %d reads without bases; add --filter min-len=1 (or higher)' % (args.trim, report['emptied']))
+        if a_report is not None and a_report['emptied'] and not keeps_bases:
+            error('ERROR: --adapter %s leaves %d reads without bases; add --filter min-len=1 (or higher)' % (adapter, a_report['emptied']))
         d_out, ls_out = ops.trim_records(ctx, d_buf, ls, 0, n, window, dst, out_bytes=size, index=True)
         ctx.sync()
         self.d_buf = d_out
         del d_buf, window, dst, ls                      # the untrimmed text is freed here (see filter_records)
         self.path, self._host = None, None              # no file holds the trimmed bytes: the host copy (`host`) comes from d_buf
-        self.trimming = {'spec': args.trim, 'criteria': explicit, 'report': report}
+        if report is not None: self.trimming = {'spec': args.trim, 'criteria': explicit, 'report': report}
+        if a_report is not None: self.adapting = {'spec': adapter, 'criteria': a_explicit, 'report': a_report}
         self._pre_index = (n, ls_out)
 
     def bin_qualities(self, census=None):
@@ -703,6 +732,9 @@ class Session:
         if self.trimming is not None:
             from . import rectrim
             self.say(rectrim.report_line(self.trimming['report']))
+        if self.adapting is not None:
+            from . import adapters
+            self.say(adapters.report_line(self.adapting['report']))
         if self.filtering is not None:
             from . import recfilter
             self.say(recfilter.report_line(self.filtering['report']))
@@ -716,6 +748,7 @@ class Session:
         }
         if binning is not None: self.config['quality_binning'] = binning
         if self.trimming is not None: self.config['trim'] = dict(self.trimming)
+        if self.adapting is not None: self.config['adapter'] = dict(self.adapting)
         if self.filtering is not None: self.config['filter'] = dict(self.filtering)
         if self.pairing is not None: self.config['paired'] = dict(self.pairing)
 
@@ -1176,6 +1209,9 @@ class Session:
             if self.trimming is not None:                     # `want` was taken from the trimmed text in HBM
                 line += '; gives back the reads as --trim %s cut them, %d of %d bases' % (
                     self.trimming['criteria'], self.trimming['report']['bases_out'], self.trimming['report']['bases_in'])
+            if self.adapting is not None:                     # ... and cut at the adapters
+                line += '; gives back the reads as --adapter %s cut them, %d of %d bases' % (
+                    self.adapting['criteria'], self.adapting['report']['bases_out'], self.adapting['report']['bases_in'])
             if self.filtering is not None:                    # `want` was taken from the filtered text in HBM
                 line += '; gives back the %d reads --filter kept of %d' % (self.filtering['report']['reads_out'], self.filtering['report']['reads_in'])
             if args.bin_qual is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
