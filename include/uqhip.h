@@ -351,6 +351,58 @@ int uq_adapter_mark(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_st
 int uq_adapter_mark_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
                          const uq_adapter_params* h_params, uint32_t* h_window, uq_adapter_report* h_report);
 
+/* ---- duplicate removal (`--dedup`; an extension: the reference stores every read it is given).  A deduplicated container
+ * is the plain encode of the deduplicated text.  The result is EXACT: no read is dropped on a hash match alone.  All arithmetic is unsigned
+ * 64-bit; mix and K are the fingerprint's (uqfp1, above), q(b) = clamp(b - 33, 0, 93) the QC tables' (uqqc1, above).  A UNIT is one record
+ * (unit = 1) or an interleaved pair (unit = 2); record first_read + i has the global index g = unit_index_base + i and belongs to unit
+ * w = g / unit (the convention of uq_filter_mark's read_index_base), so the call's first unit is unit_index_base / unit and unit w of the
+ * call holds the records first_read + w unit .. first_read + w unit + unit - 1.
+ *   COMPARED TEXT of a record with the sequence line s (length Ls, without its '\n'): c = s[0, Lc), Lc = Ls if prefix == 0, else min(Ls, prefix).
+ *     Bytes are compared as they are: case-sensitive, and N equals N.  Two units are EQUAL iff every record of the one has the same Lc and the
+ *     same c bytes as the corresponding record of the other.  Quality and QNAME lines never enter the comparison.
+ *   SEEDED LINE HASH  S = mix(seed + K); w_k = the little-endian u64 of c[8k, 8k + 8), zero-padded;
+ *     acc = SUM_k mix((w_k ^ S) + K (k + 1))  (0 for an empty text);  DL(c) = mix(acc + K Lc + 2).
+ *   UNIT HASH  unit 1: H = DL(c); unit 2: H = mix(DL(c1) + mix(DL(c2))); then H is masked to its low hash_bits bits (1 .. 64; 64 = no mask;
+ *     fewer than 64 exist for tuning and tests only: they force collisions).
+ *   SCORE  with UQ_DEDUP_BEST: min(SUM q(u[p]) over the whole quality line(s) of the unit, 2^32 - 1); otherwise 0.
+ *   KEY ROW of unit w, 16 bytes in memcmp order: H big-endian (8), 0xFFFFFFFF - score big-endian (4; four zero bytes without UQ_DEDUP_BEST),
+ *     w big-endian (4; unit numbers are below 2^32, as everywhere in this ABI).
+ *   MARK RULE over perm, the memcmp-ascending order of the call's key rows (entries are the call's unit numbers 0 .. nreads / unit - 1; a total
+ *     order, because w is in the key; what uq_argsort_rows(keys, units, 16) writes): position 0 opens a class.  For j > 0, a = perm[j - 1],
+ *     b = perm[j]: H(a) != H(b): b opens a class.  H(a) == H(b) and the units are equal: b is a DUPLICATE, every record of b gets verdict 1.
+ *     H(a) == H(b) and the units differ: b opens a class and collisions += 1.  Every record not marked duplicate gets verdict 0.
+ *   If collisions == 0 every hash run is one class and every class lies in one run: the kept units are exactly one per distinct compared text,
+ *   the first in input order, or with UQ_DEDUP_BEST the one with the highest score, ties to the lower index.  If collisions > 0 no
+ *   non-duplicate was dropped but some duplicates may have been kept: the caller repeats with seed + 1.
+ *   The DEDUPLICATED TEXT is the units whose records all have verdict 0, in input order, back to back: what uq_filter_plan and
+ *   uq_compact_records make of the verdict array.
+ * uq_dedup_report (device, 8-byte aligned; uq_dedup_report_init zeroes it): every field is a sum, so calls add.  uq_dedup_keys ADDS reads_in,
+ *   bases_in (SUM Ls) and units_in; uq_dedup_mark ADDS classes, dup_units, dup_reads (the duplicates' records), dup_bases (SUM Ls of those)
+ *   and collisions.
+ * uq_dedup_keys writes the key row of the call's unit w to d_keys + 16 w (16-byte aligned): one read of the stream, 32 B of line starts per
+ *   record; nothing else is written but the report.  uq_dedup_mark reads d_keys and d_perm (4-byte aligned), the line starts and the text of
+ *   hash-equal neighbours only, and writes d_verdict[i] for EVERY record first_read + i, i < nreads, whatever it held before.  An entry of
+ *   d_perm beyond the units is an error in the _host form; the device reads unit 0 for it (never out of bounds).  Both are queued on the
+ *   context's stream, nothing is read back.
+ * Errors: null arguments, unit not 1 or 2, nreads, first_read or unit_index_base odd with unit 2, hash_bits outside 1 .. 64, unknown flag bits,
+ * more than 2^32 units (with the base), misaligned d_keys, d_perm or d_report.  Any buffer alignment; lines shorter than 2^32 bytes; 64-bit
+ * offsets everywhere.  The _host forms: the same, sequentially, on host memory (need no GPU). */
+#define UQ_DEDUP_BEST 1u
+typedef struct uq_dedup_params { uint32_t unit, prefix, hash_bits, flags; uint64_t seed; } uq_dedup_params;
+typedef struct uq_dedup_report { uint64_t reads_in, bases_in, units_in, classes, dup_units, dup_reads, dup_bases, collisions; } uq_dedup_report;
+int uq_dedup_report_init(uq_ctx* ctx, uq_dedup_report* d_report);
+int uq_dedup_report_init_host(uq_dedup_report* h_report);
+int uq_dedup_keys(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                  uint64_t unit_index_base, const uq_dedup_params* h_params, uint8_t* d_keys, uq_dedup_report* d_report);
+int uq_dedup_keys_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                       uint64_t unit_index_base, const uq_dedup_params* h_params, uint8_t* h_keys, uq_dedup_report* h_report);
+int uq_dedup_mark(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t first_read, uint64_t nreads,
+                  uint64_t unit_index_base, const uq_dedup_params* h_params, const uint8_t* d_keys, const uint32_t* d_perm,
+                  uint8_t* d_verdict, uq_dedup_report* d_report);
+int uq_dedup_mark_host(const uint8_t* h_buf, const uint64_t* h_line_start, uint64_t first_read, uint64_t nreads,
+                       uint64_t unit_index_base, const uq_dedup_params* h_params, const uint8_t* h_keys, const uint32_t* h_perm,
+                       uint8_t* h_verdict, uq_dedup_report* h_report);
+
 /* ---- a3 / a4: the per-read packers. Replaces `encoder_fixed` (uq.py:108-182) and
  * `encoder_variable` (uq.py:188-254).  Row = sum_j code(read[j]) << (bits * (L-1-j)) [+ 1 << bits*L
  * when `variable`], big-endian, right-aligned in `*_bytes_per_row` bytes, high bytes zero. */

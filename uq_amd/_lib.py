@@ -129,6 +129,14 @@ class AdapterReport(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ('reads_in', 'bases_in', 'bases_out', 'reads_cut', 'full', 'partial', 'mate2', 'emptied', 'len_mismatch')]
 
 
+class DedupParams(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ('unit', 'prefix', 'hash_bits', 'flags')] + [('seed', C.c_uint64)]
+
+
+class DedupReport(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ('reads_in', 'bases_in', 'units_in', 'classes', 'dup_units', 'dup_reads', 'dup_bases', 'collisions')]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('len_lo', C.c_int32), ('len_hi', C.c_int32), ('n_rate', C.c_int32),
                 ('n_qual_exclusive', C.c_int32), ('dup', C.c_int32), ('dup_templates', C.c_int32),
@@ -201,6 +209,12 @@ SIGNATURES = {
     'uq_adapter_report_init_host': [_P(AdapterReport)],
     'uq_adapter_mark': [_vp, _vp, _vp, _u64, _u64, _P(AdapterParams), _vp, _vp],
     'uq_adapter_mark_host': [_vp, _vp, _u64, _u64, _P(AdapterParams), _vp, _P(AdapterReport)],
+    'uq_dedup_report_init': [_vp, _vp],
+    'uq_dedup_report_init_host': [_P(DedupReport)],
+    'uq_dedup_keys': [_vp, _vp, _vp, _u64, _u64, _u64, _P(DedupParams), _vp, _vp],
+    'uq_dedup_keys_host': [_vp, _vp, _u64, _u64, _u64, _P(DedupParams), _vp, _P(DedupReport)],
+    'uq_dedup_mark': [_vp, _vp, _vp, _u64, _u64, _u64, _P(DedupParams), _vp, _vp, _vp, _vp],
+    'uq_dedup_mark_host': [_vp, _vp, _u64, _u64, _u64, _P(DedupParams), _vp, _vp, _vp, _P(DedupReport)],
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],

@@ -448,6 +448,10 @@ def main(argv=None):
     if args.adapter is not None:
         print('ERROR: --adapter is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder does not cut the reads of its shards yet')
         return 1
+    if args.dedup is not None:
+        print('ERROR: --dedup is for the single-GPU tool (python -m uq_amd.uq): the sharded encoder does not compare the reads of one shard with '
+              'those of another yet')
+        return 1
     if args.verify or args.fingerprint:
         print('ERROR: --verify and --fingerprint are for the single-GPU tool (python -m uq_amd.uq); the fingerprint of a sharded file is the sum '
               "of its shards' (uq_fingerprint_accumulate with read_index_base), which this tool does not compute yet")

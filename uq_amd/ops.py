@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, AdapterParams, AdapterReport, UQ_NONE, load
+from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, AdapterParams, AdapterReport, DedupParams, DedupReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -565,6 +565,92 @@ def compact_records_host(data, src, dst, kept_units, out_capacity=None):
     call('uq_compact_records_host', C.c_void_p(a.ctypes.data if a.size else 0), int(a.size), C.c_void_p(src.ctypes.data if src.size else 0),
          C.c_void_p(dst.ctypes.data), int(kept_units), C.c_void_p(out.ctypes.data if out.size else 0), size if out_capacity is None else int(out_capacity))
     return out
+
+
+# ------------------------------------------------------------------ duplicate removal (include/uqhip.h)
+DEDUP_REPORT_FIELDS = tuple(k for k, _ in DedupReport._fields_)
+DEDUP_BEST = 1
+
+
+def dedup_params(unit=1, prefix=0, hash_bits=64, flags=0, seed=0):
+    """A uq_dedup_params: whole sequence lines, the full hash, the first of a class kept, seed 0 -- unless told otherwise."""
+    return DedupParams(unit, prefix, hash_bits, flags, seed)
+
+
+def dedup_report_new(ctx):
+    """A zeroed device uq_dedup_report (int64[8])."""
+    t = ctx.torch
+    d = t.empty(len(DEDUP_REPORT_FIELDS), dtype=t.int64, device=ctx.device)
+    call('uq_dedup_report_init', ctx.h, _p(d))
+    return d
+
+
+def dedup_report_fetch(ctx, d_report):
+    """The device report as a dict of Python integers (synchronises)."""
+    return dict(zip(DEDUP_REPORT_FIELDS, (int(v) for v in ctx.to_numpy(d_report).view(np.uint64))))
+
+
+def dedup_keys(ctx, d_report, buf, line_start, first_read, nreads, params, index_base=0, keys=None):
+    """The 16-byte key rows of the units of the records [first_read, first_read + nreads) of buf (a new uint8 tensor when `keys` is None),
+    their counts added into d_report (queued, nothing read back)."""
+    if keys is None: keys = ctx.empty(16 * (nreads // params.unit if params.unit in (1, 2) else nreads))
+    call('uq_dedup_keys', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), int(index_base), C.byref(params), _p(keys), _p(d_report))
+    return keys
+
+
+def dedup_mark(ctx, d_report, buf, line_start, first_read, nreads, params, keys, perm, index_base=0, verdict=None):
+    """The verdict bytes (1 = duplicate) of those records from their keys and the keys' sorted order (a new uint8 tensor when `verdict` is
+    None), the counts added into d_report (queued, nothing read back)."""
+    if verdict is None: verdict = ctx.empty(nreads)
+    call('uq_dedup_mark', ctx.h, _p(buf), _p(line_start), int(first_read), int(nreads), int(index_base), C.byref(params), _p(keys), _p(perm),
+         _p(verdict), _p(d_report))
+    return verdict
+
+
+def _dedup_report_in(report):
+    return DedupReport(*[report[k] for k in DEDUP_REPORT_FIELDS]) if report is not None else DedupReport()
+
+
+def dedup_keys_host(data, params, line_start=None, first_read=0, nreads=None, index_base=0, report=None):
+    """uq_dedup_keys_host: the same on the CPU over host bytes (needs no GPU) -> (uint8 keys [units, 16], report dict; `report`: an earlier one to add to)."""
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'dedup')
+    r = _dedup_report_in(report)
+    keys = np.zeros((nreads // params.unit if params.unit in (1, 2) else nreads, 16), dtype=np.uint8)
+    call('uq_dedup_keys_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(index_base),
+         C.byref(params), C.c_void_p(keys.ctypes.data if keys.size else 0), C.byref(r))
+    return keys, {k: int(getattr(r, k)) for k in DEDUP_REPORT_FIELDS}
+
+
+def dedup_order_host(keys):
+    """The memcmp-ascending order of host key rows, as uq_argsort_rows gives it on the device (uint32)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 16)
+    return np.argsort(keys.view('V16').ravel(), kind='stable').astype(np.uint32)
+
+
+def dedup_mark_host(data, params, keys, perm, line_start=None, first_read=0, nreads=None, index_base=0, report=None):
+    """uq_dedup_mark_host -> (uint8 verdicts, report dict)."""
+    a, ls, nreads = _host_records(data, line_start, first_read, nreads, 'dedup')
+    r = _dedup_report_in(report)
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    verdict = np.full(nreads, 0xEE, dtype=np.uint8)
+    call('uq_dedup_mark_host', C.c_void_p(a.ctypes.data if a.size else 0), C.c_void_p(ls.ctypes.data), int(first_read), int(nreads), int(index_base),
+         C.byref(params), C.c_void_p(keys.ctypes.data if keys.size else 0), C.c_void_p(perm.ctypes.data if perm.size else 0),
+         C.c_void_p(verdict.ctypes.data if nreads else 0), C.byref(r))
+    return verdict, {k: int(getattr(r, k)) for k in DEDUP_REPORT_FIELDS}
+
+
+DEDUP_SEEDS = 8
+
+
+def dedup_verdicts(run_seed):
+    """The driver loop of --dedup: run_seed(seed) -> (verdict, report) of one keys / sort / mark round; while the round's hashes collided it is
+    repeated with seed + 1.  -> (verdict, report, the seed that held); DEDUP_SEEDS collisions in a row are a UqError."""
+    from .errors import UqError
+    for seed in range(DEDUP_SEEDS):
+        verdict, report = run_seed(seed)
+        if report['collisions'] == 0: return verdict, report, seed
+    raise UqError('ERROR: --dedup: %d hash seeds in a row collided' % DEDUP_SEEDS)
 
 
 # ------------------------------------------------------------------ read trimming (include/uqhip.h, DESIGN.md section 28)

@@ -105,6 +105,8 @@ def build_parser():
     p.add_argument('--trim', action='store', default=None, metavar='SPEC', help=rectrim.HELP)
     from . import adapters
     p.add_argument('--adapter', action='store', default=None, metavar='SPEC', help=adapters.HELP)
+    from . import recdedup
+    p.add_argument('--dedup', action='store', default=None, metavar='SPEC', help=recdedup.HELP)
     p.add_argument('--mate2', action='store', default=None, metavar='R2.fastq',
                    help='paired-end input: -i is R1, this is R2 (plain, BGZF or other gzip, each by its content).  The read counts must be equal and '
                         'read r of R2 must be the mate of read r of R1 (same QNAME up to the first space or tab, /1 with /2 allowed); the two '
@@ -175,6 +177,9 @@ def validate_args(args):
         if args.decode: error('ERROR: --adapter cuts reads before an encode stores them: the text --decode writes is what the container holds')
         if adapter_criteria(args.adapter)[0]['seq2'] is not None and args.mate2 is None and not args.interleaved:
             error('ERROR: --adapter %s: seq2 is the second mates\' adapter: use it together with --mate2 or --interleaved' % args.adapter)
+    if args.dedup is not None:
+        if args.decode: error('ERROR: --dedup drops reads before an encode stores them: the text --decode writes is what the container holds')
+        dedup_criteria(args.dedup)
     mate2, interleaved, split = args.mate2, args.interleaved, args.split_mates
     if mate2 is not None and interleaved:
         error('ERROR: --mate2 and --interleaved are two forms of the same input: give R1 with -i and R2 with --mate2, or one interleaved file with --interleaved')
@@ -202,6 +207,12 @@ def filter_criteria(spec):
     """--filter SPEC -> (the criteria of uq_filter_params, the explicit form of the spec); a bad spec is a UqError."""
     from . import recfilter
     return recfilter.parse(spec), recfilter.explicit(spec)
+
+
+def dedup_criteria(spec):
+    """--dedup SPEC -> (prefix and flags of uq_dedup_params, the explicit form of the spec); a bad spec is a UqError."""
+    from . import recdedup
+    return recdedup.parse(spec), recdedup.explicit(spec)
 
 
 def trim_steps(spec):
@@ -264,6 +275,7 @@ class Session:
         self.bin_qual_ranges = None    # --bin-qual: the explicit form of the spec
         self.binned_changed = 0    # --bin-qual: quality characters this session's binning changed
         self.filtering = None      # --filter: config.json's "filter" value (spec, criteria, unit, report)
+        self.deduping = None       # --dedup: config.json's "dedup" value (spec, criteria, unit, seed, report)
         self.trimming = None       # --trim: config.json's "trim" value (spec, criteria, report)
         self.adapting = None       # --adapter: config.json's "adapter" value (spec, criteria, report)
         self._pre_index = None     # --trim, --filter: (reads, record index) of the buffer a paired loader or trim_records hands on, until the next step of load_device takes it
@@ -370,12 +382,12 @@ class Session:
         """The input of an encode (or of --fingerprint / --qc) in HBM: one file, two mates interleaved on the device, or one interleaved file."""
         args = self.args
         if args.mate2 is not None: return self.load_pairs(args.input, args.mate2)
-        if args.interleaved and args.filter is not None: return self.load_interleaved_filtered(args.input)
+        if args.interleaved and (args.filter is not None or args.dedup is not None): return self.load_interleaved_filtered(args.input)
         self.load(args.input)
         if args.interleaved: self.check_interleaved()
 
     def load_interleaved_filtered(self, path):
-        """--interleaved --filter: the mates are checked on the input as it is given, BEFORE load_device drops reads: text to HBM, index, even
+        """--interleaved --filter (or --dedup): the mates are checked on the input as it is given, BEFORE load_device drops reads: text to HBM, index, even
         read count, uq_mate_check, then load_device (which filters, and checks the mates of what is left once more)."""
         d_buf = self.text_to_device(path)
         n, ls = self.indexed(d_buf, None)
@@ -434,7 +446,7 @@ class Session:
 
     def load_device(self, d_buf=None, census=None):
         """The same for FASTQ bytes that are already in HBM (a uint8 device tensor; `census`: an ops.ChunkedCensus of it whose chunks have
-        all been queued -- load() queues them behind the PCIe copies).  --trim, --filter, --bin-qual first, in that order; then the line count alone (--fingerprint, --qc),
+        all been queued -- load() queues them behind the PCIe copies).  --trim, --filter, --dedup, --bin-qual first, in that order; then the line count alone (--fingerprint, --qc),
         or the queued step bench.py times, or -- where that does not hold for this file -- the same two reads with the record index,
         or -- where that has no kernel either, and under --multi-pass -- the plain statistics pass.  Same results whichever path."""
         self._reset_load_state()
@@ -446,8 +458,11 @@ class Session:
         if self.args.filter is not None:
             self.filter_records(census)
             census = None                                # (the kept reads in a buffer of their own; the census of the unfiltered text has been closed)
+        if self.args.dedup is not None:
+            self.dedup_records(census)
+            census = None                                # (likewise)
         trimmed = None
-        if self._pre_index is not None:                  # --trim without --filter: the index uq_trim_records wrote is the trimmed text's
+        if self._pre_index is not None:                  # --trim without --filter or --dedup: the index uq_trim_records wrote is the trimmed text's
             (n, ls), self._pre_index = self._pre_index, None
             trimmed = (4 * n, ls)
             del ls
@@ -566,6 +581,45 @@ class Session:
         del d_buf, src, dst, verdict, ls               # the unfiltered text is freed here: the loaders of this class keep no name of it (a caller that passed its own tensor to load_device keeps that)
         self.path, self._host = None, None             # no file holds the filtered bytes: the host copy (`host`) comes from d_buf
         self.filtering = {'spec': args.filter, 'criteria': explicit, 'unit': unit, 'report': report}
+        if unit == 2:
+            nk, ls_k = self.indexed(d_out, None)
+            self.require_mates(d_out, ls_k, 0, 2, d_out, ls_k, 1, 2, nk // 2)
+
+    def dedup_records(self, census=None):
+        """--dedup, behind filter_records and in front of bin_qualities (duplicates are judged on the reads as trimmed, cut and filtered; keep=best
+        on the qualities as given): the units of self.d_buf get their sort keys (uq_dedup_keys), the keys are sorted (uq_argsort_rows), hash-equal
+        neighbours are compared byte for byte (uq_dedup_mark) -- with the next seed while two different sequences shared a hash (ops.dedup_verdicts)
+        -- and the units that repeat no earlier one are copied back to back into a new buffer (uq_filter_plan with a scratch report,
+        uq_compact_records), which replaces self.d_buf; the old one is freed, by the rules filter_records states.  Needs the record index
+        (`_pre_index` if the trimmer left one, else the census, closed here, + uq_index_lines).  Of a paired text the mates are checked once
+        more on what is left, and that report is what `pairing` holds."""
+        ops, ctx, args = self.ops, self.ctx, self.args
+        d_buf = self.d_buf
+        criteria, explicit = dedup_criteria(args.dedup)
+        unit = 2 if (args.mate2 is not None or args.interleaved) else 1
+        if self._pre_index is not None: (n, ls), self._pre_index = self._pre_index, None
+        else:
+            nlines = census.end() if census is not None else (ops.count_lines(ctx, d_buf) if d_buf.numel() else 0)
+            if census is not None: census.buf = None     # (closed: it lets go of the text with its duplicates)
+            n = whole_records(nlines)
+            ls = ops.index_lines(ctx, d_buf, nlines)
+        if n % unit: error('ERROR: --interleaved: the input holds %d reads, an odd number: R1 and R2 do not alternate' % n)
+
+        def run_seed(seed):
+            params = ops.dedup_params(unit=unit, prefix=criteria['prefix'], flags=criteria['flags'], seed=seed)
+            d_report = ops.dedup_report_new(ctx)
+            keys = ops.dedup_keys(ctx, d_report, d_buf, ls, 0, n, params)
+            perm = ops.argsort_rows(ctx, keys, n // unit, 16)
+            verdict = ops.dedup_mark(ctx, d_report, d_buf, ls, 0, n, params, keys, perm)
+            return verdict, ops.dedup_report_fetch(ctx, d_report)
+        verdict, report, seed = ops.dedup_verdicts(run_seed)
+        src, dst, kept, size = ops.filter_plan(ctx, ops.filter_report_new(ctx), ls, 0, n, unit, verdict)
+        d_out = ops.compact_records(ctx, d_buf, src, dst, kept, out_bytes=size)
+        ctx.sync()
+        self.d_buf = d_out
+        del d_buf, src, dst, verdict, ls               # the text with its duplicates is freed here (see filter_records)
+        self.path, self._host = None, None             # no file holds the deduplicated bytes: the host copy (`host`) comes from d_buf
+        self.deduping = {'spec': args.dedup, 'criteria': explicit, 'unit': unit, 'seed': seed, 'report': report}
         if unit == 2:
             nk, ls_k = self.indexed(d_out, None)
             self.require_mates(d_out, ls_k, 0, 2, d_out, ls_k, 1, 2, nk // 2)
@@ -738,6 +792,9 @@ class Session:
         if self.filtering is not None:
             from . import recfilter
             self.say(recfilter.report_line(self.filtering['report']))
+        if self.deduping is not None:
+            from . import recdedup
+            self.say(recdedup.report_line(self.deduping['report']))
         self.report(prefix, suffix, separators)
         self.config = {
             'base_distribution': d['base_distribution'], 'qual_distribution': d['qual_distribution'],
@@ -750,6 +807,7 @@ class Session:
         if self.trimming is not None: self.config['trim'] = dict(self.trimming)
         if self.adapting is not None: self.config['adapter'] = dict(self.adapting)
         if self.filtering is not None: self.config['filter'] = dict(self.filtering)
+        if self.deduping is not None: self.config['dedup'] = dict(self.deduping)
         if self.pairing is not None: self.config['paired'] = dict(self.pairing)
 
     def report(self, prefix, suffix, separators):
@@ -1214,6 +1272,9 @@ class Session:
                     self.adapting['criteria'], self.adapting['report']['bases_out'], self.adapting['report']['bases_in'])
             if self.filtering is not None:                    # `want` was taken from the filtered text in HBM
                 line += '; gives back the %d reads --filter kept of %d' % (self.filtering['report']['reads_out'], self.filtering['report']['reads_in'])
+            if self.deduping is not None:                     # ... and from the deduplicated text
+                line += '; gives back the %d reads --dedup kept of %d' % (
+                    self.deduping['report']['reads_in'] - self.deduping['report']['dup_reads'], self.deduping['report']['reads_in'])
             if args.bin_qual is not None:                     # `want` was taken from the binned stream in HBM: the container gives back the binned reads
                 line += '; qualities binned by --bin-qual %s, %d characters changed' % (args.bin_qual, self.binned_changed_in_file())
             show(line)
