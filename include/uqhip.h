@@ -441,6 +441,19 @@ int uq_pack_stats(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_star
 int uq_pack_stats_async(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_start, uint64_t capacity_reads,
                         const uq_pack_params* h_guess, uint8_t* d_dna, uint8_t* d_qual, uint64_t* d_bad,
                         uq_stats* d_stats, int* h_fused);
+/* The tile geometry the pack kernels run these parameters at (csrc/pack_geometry.h; host only, no context): `form` says which kernel --
+ * 0 the plain pack, UQ_PACK_FORM_STATS the fused pack + statistics kernel, with UQ_PACK_FORM_QNAME its QNAME phase, with UQ_PACK_FORM_LISTS
+ * the line starts from the census's lists (d_line_start == NULL).  tiled = 0: the longest record fits no tile (the exact kernel packs; no fused
+ * form) and the other fields are zero.  Else reads per tile (R) and per piece of a tile beyond the stage (Rs), lanes per read (P) over G groups of
+ * eight symbols, the staging region and the out tile in bytes, the copies of the count table, the workgroup's LDS (static and dynamic) and the
+ * workgroups a CU's LDS holds; tile64 = 1: the 64-read tile. */
+#define UQ_PACK_FORM_STATS 1u
+#define UQ_PACK_FORM_QNAME 2u
+#define UQ_PACK_FORM_LISTS 4u
+typedef struct uq_pack_tile_geom {
+    uint32_t tiled, tile64, R, Rs, P, G, stage_bytes, out_bytes, copies, lds_bytes, wg_per_cu, reserved;
+} uq_pack_tile_geom;
+int uq_pack_tile_geometry(const uq_pack_params* h_params, uint32_t form, uq_pack_tile_geom* h_out);
 
 /* ---- a9 / a11: the eight --pattern byte layouts.  Replaces numpy.rot90 + ascontiguousarray /
  * asfortranarray + the payload write of numpy.save (uq.py:263-270) and, inverse, numpy.load +

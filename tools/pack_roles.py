@@ -46,6 +46,8 @@ assert lib.uq_pack_role_clock(out, 0) == 0
 launches = RUNS - WARM
 call_ms = sum(ms) / len(ms)
 names = ['A + barrier 1', 'B (work)', 'wait at barrier 2', 'wait for next tile', 'C (copy-out)']
+try: print('tile geometry:', ops.pack_tile_geometry(guess, stats=True, qname=qn, lists=True))
+except AttributeError: print('tile geometry: not reported (a library from before uq_pack_tile_geometry)')
 print('%s: %d reads, pack + statistics%s call %.4f ms (min %.4f) over %d launches' % (os.path.basename(_lib.LIB_PATH), n, ' + QNAME' if qn else '', call_ms, min(ms), launches))
 # a wave's five sums add up to its whole tile loop, which is the launch but for its prologue and epilogue: cycles per microsecond from that
 pack_total = sum(out[k] for k in range(5)) / max(out[6], 1)

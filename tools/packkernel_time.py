@@ -29,4 +29,6 @@ for it in range(12):
     census.wait(); torch.cuda.synchronize()
     if it >= 2: ms.append(e0.elapsed_time(e1))
     del sp, fq, st
+try: print('tile geometry:', ops.pack_tile_geometry(guess, stats=True, qname=qn, lists=True))
+except AttributeError: print('tile geometry: not reported (a library from before uq_pack_tile_geometry)')
 print('%s: pack + statistics%s call %.4f ms (min %.4f) over %d runs' % (os.path.basename(os.environ.get('UQ_LIB_PATH', 'libuqhip.so')), ' + QNAME' if qn else '', sum(ms) / len(ms), min(ms), len(ms)))

@@ -28,6 +28,14 @@ class PackParams(C.Structure):
                 ('max_record_bytes', C.c_int32), ('dna_max', C.c_int32), ('avg_record_bytes', C.c_int32)]
 
 
+class PackTileGeom(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ('tiled', 'tile64', 'R', 'Rs', 'P', 'G', 'stage_bytes', 'out_bytes', 'copies', 'lds_bytes', 'wg_per_cu',
+                                          'reserved')]
+
+    def __repr__(self):
+        return 'PackTileGeom(%s)' % ', '.join('%s=%d' % (k, getattr(self, k)) for k, _ in self._fields_[:-1])
+
+
 class UnpackParams(C.Structure):
     _fields_ = [('base_char', C.c_uint8 * 256), ('qual_char', C.c_uint8 * 256), ('qual_n_base', C.c_uint8 * 256),
                 ('bits_per_base', C.c_int32), ('bits_per_quality', C.c_int32), ('variable', C.c_int32),
@@ -218,6 +226,7 @@ SIGNATURES = {
     'uq_pack': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp],
     'uq_pack_stats': [_vp, _vp, _vp, _u64, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
     'uq_pack_stats_async': [_vp, _vp, _vp, _u64, _P(PackParams), _vp, _vp, _vp, _vp, _P(_int)],
+    'uq_pack_tile_geometry': [_P(PackParams), _u32, _P(PackTileGeom)],
     'uq_pattern': [_vp, _vp, _u64, _u32, _int, _vp],
     'uq_unpattern': [_vp, _vp, _u64, _u32, _int, _vp],
     'uq_argsort_rows': [_vp, _vp, _u64, _u32, _vp],

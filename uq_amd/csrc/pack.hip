@@ -25,6 +25,7 @@
 #include "swar.h"
 #include "lines.h"
 #include "histo.h"
+#include "pack_geometry.h"
 
 // PK_ROLE_CLOCK (a variant build: tools/variants.sh pack.hip clock -DPK_ROLE_CLOCK; tools/pack_roles.py reads it): every wave of pack_tile_kernel reads the
 // cycle counter at five points of a tile -- (1) behind barrier 1, (2) arriving at barrier 2, (3) behind it, (4) behind the wait for the next tile's
@@ -282,9 +283,12 @@ __device__ __forceinline__ void qname_tile(const uint8_t* stage, const uint32_t*
     if (f) atomicOr(&s->flags, f);
 }
 
-constexpr int PK_NV = 5;   // 16-byte loads per lane per tile: a tile spans at most PK_NV * 256 * 16 = 20 KiB
-constexpr int PK_NV_STATS = 4;   // the fused pack + statistics kernel keeps a few KiB of LDS for its count table: 16 KiB tiles, same occupancy
-constexpr uint32_t pk_stage_bytes(bool stats) { return (uint32_t)(stats ? PK_NV_STATS : PK_NV) * PK_THREADS * 16 + 32; }   // the staging region: what the lanes hold in flight, and slack for the windows
+// (the numbers themselves, and the choice between the two tiles, are pack_geometry.h's)
+constexpr int PK_NV = pkgeom::NV_PLAIN;   // 16-byte loads per lane per tile: a tile spans at most PK_NV * 256 * 16 = 20 KiB
+constexpr int PK_NV_STATS = pkgeom::NV_STATS;   // the fused pack + statistics kernel keeps a few KiB of LDS for its count table: 16 KiB tiles, same occupancy
+constexpr int PK_NV_T64 = pkgeom::NV_TILE64;    // the 64-read tile: a 22 KiB stage, the sixth vector held by the lanes whose share of it lies inside the tile
+constexpr uint32_t pk_stage_bytes(bool stats, bool t64 = false) { return pkgeom::stage_bytes(stats, t64); }   // the staging region: what the lanes hold in flight, and slack for the windows
+static_assert(PK_THREADS == (int)pkgeom::THREADS, "pack_geometry.h is written for this workgroup");
 // Its counts are taken on the CODES the lookup-free conversion has just produced (bin = base code << 6 | quality code: two
 // instructions per four pairs instead of re-deriving bins from the characters), into an LDS table (3-bit bases: four copies);
 // code 0 fill pairs of a read's partial top group and the N-trick positions (counted as their substitute there) are taken off
@@ -294,14 +298,14 @@ constexpr uint32_t pk_stage_bytes(bool stats) { return (uint32_t)(stats ? PK_NV_
 // copy for the 2-bit bases -- a counter's address is then `byte of the bin word << 2` plus an immediate, one SDWA shift per atomic, 10 VALU
 // instructions per group of eight pairs instead of 20; the lanes that meet in a counter cost more than that saves, 1.66 -> 1.71 ms: PK_ONE_COPY.)
 #ifdef PK_ONE_COPY
-constexpr int pks_copies(int bd, bool four_wg) { return bd == 3 ? 4 : 1; }
+constexpr int pks_copies(int bd, bool four_wg, bool t64 = false) { return bd == 3 ? 4 : 1; }
 #else
 // (the forms built for four workgroups per CU -- QNAME phase or N-trick -- have the LDS for eight copies of the 256 bins: 1.56 -> 1.54 ms, two copies 1.60;
-// the others would drop from four workgroups per CU to three)
-constexpr int pks_copies(int bd, bool four_wg) { return bd == 2 && four_wg ? 8 : 4; }
+// the others would drop from four workgroups per CU to three; the 64-read tile spends that LDS on its stage and keeps four)
+constexpr int pks_copies(int bd, bool four_wg, bool t64 = false) { return bd == 2 && four_wg && !t64 ? 8 : 4; }
 #endif
 constexpr uint32_t pks_bins(int bd) { return bd == 3 ? 512u : 256u; }     // bin = base code << 6 | quality code (3-bit bases: nine bits)
-constexpr uint32_t pks_words(int bd, bool four_wg) { return pks_bins(bd) * pks_copies(bd, four_wg) + 128; }
+constexpr uint32_t pks_words(int bd, bool four_wg, bool t64 = false) { return pks_bins(bd) * pks_copies(bd, four_wg, t64) + 128; }
 
 // The queued forms take their line starts from the census's lists instead of an expanded index (lines.h): a record per pack tile (TileRec): the start of
 // the tile's first record (entry `ntiles`: the end of the last record), where the newline in front of it sits (census tile,
@@ -314,6 +318,7 @@ struct TileRec { uint64_t start; uint32_t T, A, B, pad; };
 // for four workgroups per CU: held in uniform registers over the loop it is spilled to vector lanes and moved back and forth by every tile.
 // (Not the census's offsets: a pointer read back from LDS is a generic one, and the loads through it would be flat loads.)
 struct PkParked { unsigned long long* bad; uq_stats* st; uq_qname_fused* qf; uint64_t first, nb, nl_total; uint32_t Rs, pad; };
+static_assert(sizeof(QnLds) == pkgeom::QNLDS_BYTES && ((sizeof(PkParked) + 15) & ~size_t(15)) == pkgeom::PARKED_BYTES, "pack_geometry.h counts these bytes");
 struct PackLists {
     CensusView cv;                             // cv.list == nullptr: the expanded index (`ls`) is used
     const uint32_t* over;                      // the census's overflow word: a tile held more newlines than its list (the lists are not usable)
@@ -364,7 +369,10 @@ __global__ __launch_bounds__(256) void tile_origin_kernel(CensusView cv, const u
 // workgroups per CU: the parser's registers come on top of a tile in flight.
 // VAR (variable-length tables, the queued fused forms): the lanes of a read visit only the groups that hold a symbol or the sentinel; the
 // rows' empty upper parts (rows are sized for the longest read) are never stored -- the copy-out of the tile before has cleared the LDS image.
-template <int BD, int BQ, bool NTRICK, bool FAST, bool STATS, bool QN, bool LISTS = false, bool VAR = false>
+// T64 (the 64-read tile of pack_geometry.h; forms built for four workgroups per CU): a 22 KiB stage, six vectors a lane in flight, four copies of the
+// count table.  A tile has 4 x 64 + 1 line starts for 256 lanes: the first is the tile's own start -- skew bytes into the stage, no load -- and lane
+// k fetches line start k + 1.
+template <int BD, int BQ, bool NTRICK, bool FAST, bool STATS, bool QN, bool LISTS = false, bool VAR = false, bool T64 = false>
 __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void pack_tile_kernel(const uint8_t* __restrict__ buf,
                                                                const uint64_t* __restrict__ ls, uint64_t first,
                                                                uint64_t n, PackLut lut, PackGeom g,
@@ -373,10 +381,11 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
                                                                uq_stats* __restrict__ st, const unsigned long long* __restrict__ d_async,
                                                                uq_qname_fused* __restrict__ qf, uint32_t* __restrict__ qvals, uint64_t qpitch, PackLists pl,
                                                                const TileRec* __restrict__ trec) {      // trec: [pack tiles + 1] with pl (a restrict parameter of its own: the records are read through the scalar cache, like `ls`)
-    constexpr int NV = STATS ? PK_NV_STATS : PK_NV;
+    constexpr int NV = T64 ? PK_NV_T64 : STATS ? PK_NV_STATS : PK_NV;
+    static_assert(!T64 || (STATS && (NTRICK || QN) && BD == 2 && !VAR), "the 64-read tile exists for the fixed-row forms built for four workgroups per CU");
     extern __shared__ __align__(16) uint8_t smem[];
     // (everything in front of the out tile sits at an offset the compiler knows: one uniform address to hold over the tile loop instead of five)
-    constexpr uint32_t STAGE_BYTES = pk_stage_bytes(STATS);      // = g.stage_bytes
+    constexpr uint32_t STAGE_BYTES = pk_stage_bytes(STATS, T64);      // = g.stage_bytes
     uint8_t* stage = smem + 16;                       // reads of up to 8 bytes below offset 0 stay in bounds
     int16_t* l_dna = (int16_t*)(stage + STAGE_BYTES);
     int16_t* l_qual = l_dna + 256;
@@ -392,10 +401,10 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
     RecordAcc acc;
     bool incomplete = false;
     constexpr bool FOUR_WG = STATS && (NTRICK || QN);
-    constexpr int PKS_COPIES = pks_copies(BD, FOUR_WG);
-    __shared__ uint32_t cnt_tab[STATS ? pks_words(BD, FOUR_WG) : 1];      // [bins][PKS_COPIES], then [128] N-trick base by quality character
+    constexpr int PKS_COPIES = pks_copies(BD, FOUR_WG, T64);
+    __shared__ uint32_t cnt_tab[STATS ? pks_words(BD, FOUR_WG, T64) : 1];      // [bins][PKS_COPIES], then [128] N-trick base by quality character
     uint32_t fill_pairs = 0, n_pairs = 0;                        // pairs counted in bin 0 / bin n_code that were fills / N-trick positions
-    constexpr uint32_t PKS_BINS = pks_bins(BD), PKS_WORDS = pks_words(BD, FOUR_WG);
+    constexpr uint32_t PKS_BINS = pks_bins(BD), PKS_WORDS = pks_words(BD, FOUR_WG, T64);
     if (STATS) for (uint32_t i = tid; i < PKS_WORDS; i += PK_THREADS) cnt_tab[i] = 0;       // the first tile's barrier orders it
     if (VAR) for (uint32_t i = tid; i < (g.out_bytes >> 4); i += PK_THREADS) ((uint4*)out_d)[i] = make_uint4(0, 0, 0, 0);       // (likewise; every copy-out clears what it reads)
     bool qn_on = false;
@@ -520,17 +529,18 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         const uint4* src = (const uint4*)(buf + ((int64_t)b.g0 - (int64_t)x.skew));      // (pointer arithmetic on the kernel's own argument, not an integer cast back to a pointer: the loads are global_load, not flat_load -- a flat access counts in lgkmcnt as well and returns out of order, so every wait for LDS data also waited for the tile in flight)
 #pragma unroll
         for (int u = 0; u < NV; ++u) { const uint32_t i = u * PK_THREADS + tid; if (i < x.nvec) x.v[u] = src[i]; }
-        if (tid <= 4 * x.Rt) {
+        const uint32_t e = T64 ? tid + 1 : tid;       // the line start of the tile this lane fetches (T64: start 0 is the tile's own, phase A forms it)
+        if (T64 ? tid < 4 * x.Rt : tid <= 4 * x.Rt) {
             if constexpr (lists) {
-                // the newline in front of line start `tid` of the tile: slot kk - 1 + tid of census tile T, counted on through T + 1, T + 2
-                uint32_t idx = (b.pA & 0xFFFFu) + tid, t = b.pT;          // (slot + 1)
+                // the newline in front of line start `e` of the tile: slot kk - 1 + e of census tile T, counted on through T + 1, T + 2
+                uint32_t idx = (b.pA & 0xFFFFu) + e, t = b.pT;          // (slot + 1)
                 const uint32_t c0 = b.pA >> 16, c1 = b.pB & 0xFFFFu;
                 if (idx > c0) { idx -= c0; ++t; if (idx > c1) { idx -= c1; ++t; } }
                 // the list entry stays as loaded until the next tile's phase A adds it up: arithmetic on it HERE would wait for the load -- and
                 // with it for the tile's bytes requested above
                 x.mrel = x.skew - (uint32_t)b.g0 + (idx == 0 ? 0u : (uint32_t)t * (uint32_t)CV_TILE - pl.cv.mis + 1u);      // (modulo 2^32: a tile spans less)
                 x.mraw = idx == 0 ? 0u : (uint32_t)pl.cv.list[(uint64_t)t * CV_LIST_CAP + (idx - 1)];
-            } else x.m0 = ls[4 * (first + (uint64_t)rfirst) + tid];
+            } else x.m0 = ls[4 * (first + (uint64_t)rfirst) + e];
         }
         return x;
     };
@@ -549,7 +559,10 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         uint8_t* out_q = out_d + ((Rt * g.Cd + 15) & ~15u);
         // ---- A: registers -> LDS
         if (cur.ok) {
-            if (tid <= 4 * Rt) meta[tid] = lists ? cur.mrel + cur.mraw : (uint32_t)(cur.m0 - cur.g0) + cur.skew;
+            if constexpr (T64) {
+                if (tid < 4 * Rt) meta[tid + 1] = lists ? cur.mrel + cur.mraw : (uint32_t)(cur.m0 - cur.g0) + cur.skew;
+                if (tid == 0) meta[0] = cur.skew;
+            } else if (tid <= 4 * Rt) meta[tid] = lists ? cur.mrel + cur.mraw : (uint32_t)(cur.m0 - cur.g0) + cur.skew;
 #pragma unroll
             for (int u = 0; u < NV; ++u) { const uint32_t i = u * PK_THREADS + tid; if (i < cur.nvec) ((uint4*)stage)[i] = cur.v[u]; }
         } else {
@@ -562,7 +575,8 @@ __global__ __launch_bounds__(PK_THREADS, (STATS && (NTRICK || QN)) ? 4 : 5) void
         PK_CLOCK(1);
         // The parser's wave reaches barrier 2 last -- the three waves that pack wait there for 15 % of a tile (tools/pack_roles.py) -- although it
         // issues fewer instructions than they do: it shares its SIMD with three packing waves of the CU's other workgroups, which have that time to spare.
-        // From barrier 1 until its lines are parsed it asks for the SIMD's issue slots first (PK_QN_NO_PRIO: as before; 1.42 -> 1.37 ms).
+        // From barrier 1 until its lines are parsed it asks for the SIMD's issue slots first (PK_QN_NO_PRIO: as before; 1.42 -> 1.37 ms, and
+        // with 64 reads a tile, the parser's wave full, 1.20 -> 1.13 ms: DESIGN 33).
 #ifndef PK_QN_NO_PRIO
         if (STATS && QN && tid >= PK_THREADS - 64) __builtin_amdgcn_s_setprio(3);
 #endif
@@ -988,6 +1002,20 @@ PackKernel pick_stats_kernel_q(int bq, bool ntrick) {
     switch (bq) { UQ_PS(1) UQ_PS(2) UQ_PS(3) UQ_PS(4) UQ_PS(5) default: return ntrick ? pack_tile_kernel<BD, 6, true, true, true, QN, LISTS, VAR> : pack_tile_kernel<BD, 6, false, true, true, QN, LISTS, VAR>; }
 #undef UQ_PS
 }
+// the instances of the 64-read tile: 2-bit bases, the QNAME phase or the N-trick (both: four workgroups per CU), fixed rows
+template <bool NTRICK, bool QN, bool LISTS>
+PackKernel pick_tile64_q(int bq) {
+#define UQ_PS(B) case B: return pack_tile_kernel<2, B, NTRICK, true, true, QN, LISTS, false, true>;
+    switch (bq) { UQ_PS(1) UQ_PS(2) UQ_PS(3) UQ_PS(4) UQ_PS(5) default: return pack_tile_kernel<2, 6, NTRICK, true, true, QN, LISTS, false, true>; }
+#undef UQ_PS
+}
+PackKernel pick_tile64(int bq, bool ntrick, bool qn, bool lists) {
+    if (qn) {
+        if (ntrick) return lists ? pick_tile64_q<true, true, true>(bq) : pick_tile64_q<true, true, false>(bq);
+        return lists ? pick_tile64_q<false, true, true>(bq) : pick_tile64_q<false, true, false>(bq);
+    }
+    return lists ? pick_tile64_q<true, false, true>(bq) : pick_tile64_q<true, false, false>(bq);        // (four workgroups per CU without the QNAME phase: the N-trick forms)
+}
 PackKernel pick_stats_kernel(int bd, int bq, bool ntrick, bool qn, bool lists, bool var) {
     if (var && lists) {                           // variable lengths in the queued forms: the dealing of phase B (VAR)
         if (qn) return bd == 3 ? pick_stats_kernel_q<3, true, true, true>(bq, ntrick) : pick_stats_kernel_q<2, true, true, true>(bq, ntrick);
@@ -1016,6 +1044,20 @@ PackKernel pick_kernel(int bd, int bq, bool ntrick, bool fast) {
     }
 }
 }  // namespace
+
+// what pack_geometry.h asks about a call: the parameters' share, and the form of the kernel
+static pkgeom::Query pk_query(const uq_pack_params* hp, bool stats, bool qn, bool lists) {
+    pkgeom::Query q{};
+    q.bits_per_base = (uint32_t)hp->bits_per_base; q.Cd = (uint32_t)hp->dna_bytes_per_row; q.Cq = (uint32_t)hp->quality_bytes_per_row;
+    q.dna_max = (uint32_t)hp->dna_max; q.variable = hp->variable ? 1 : 0;
+    q.max_record_bytes = hp->max_record_bytes > 0 ? (uint32_t)hp->max_record_bytes : 0; q.avg_record_bytes = hp->avg_record_bytes > 0 ? (uint32_t)hp->avg_record_bytes : 0;
+    q.stats = stats; q.qn = stats && qn; q.lists = stats && lists;
+    for (int i = 0; i < 256; ++i) if (hp->dna_code[i] < 0 && hp->n_qual[i] >= 0) q.ntrick = true;
+#ifdef PK_ONE_COPY
+    q.one_copy = true;
+#endif
+    return q;
+}
 
 // d_stats == nullptr: plain pack.  Otherwise the fused pack + statistics kernel, if this geometry has one
 // (*h_fused = 1); if not, nothing is launched and *h_fused = 0.
@@ -1066,13 +1108,13 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
     UQ_REQUIRE(fill_d >= 0 && fill_q >= 0, "uq_pack: the alphabets need a symbol with code 0");
     UQ_REQUIRE(max_d < (1 << bd), "uq_pack: a DNA code does not fit %u bits", bd);
     const bool carry = max_q >= (1 << bq);   // Q9: N quality code == 2^b (or beyond)
-    // A tile is at most PK_NV * 256 * 16 B = 20 KiB of FASTQ (what one workgroup keeps in flight in registers).  Records
+    // A standard tile is at most PK_NV * 256 * 16 B = 20 KiB of FASTQ (what one workgroup keeps in flight in registers).  Records
     // that do not fit (reads beyond ~10 kbp: long-read platforms) take the exact thread-per-read kernel too: slow, never wrong.
-    const uint32_t stage_cap = (d_stats ? PK_NV_STATS : PK_NV) * PK_THREADS * 16;
-    const uint32_t rec = (uint32_t)hp->max_record_bytes;
-    UQ_REQUIRE(rec >= 4, "uq_pack: max_record_bytes not set (take it from uq_stats)");
+    UQ_REQUIRE(hp->max_record_bytes >= 4, "uq_pack: max_record_bytes not set (take it from uq_stats)");
+    // reads per tile and piece, lanes per read, the stage, the count table's copies, the LDS: pack_geometry.h
+    const pkgeom::Geometry tg = pkgeom::tile_geometry(pk_query(hp, d_stats != nullptr, d_q != nullptr, use_lists));
 
-    if (carry || rec + 64 > stage_cap) {
+    if (carry || !tg.tiled) {
         if (d_stats) return 0;                   // no fused form of the exact kernel
         uint32_t blocks = (uint32_t)((nreads + 255) / 256);
         pack_carry_kernel<<<blocks, 256, 0, ctx->stream>>>(d_buf, d_line_start, first_read, nreads, lut, bd, bq, Cd, Cq,
@@ -1088,41 +1130,11 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
     g.magicG = magic_u32(g.G);
     g.fill_d = 0x01010101u * (uint32_t)fill_d;
     g.fill_q = 0x01010101u * (uint32_t)fill_q;
-    // Reads per tile.  Rs (from the LONGEST record) always fits the stage; R comes from the AVERAGE record (+15 %) when the
-    // caller knows it -- variable-length files fill the stage instead of leaving room for 48 longest reads -- and a tile
-    // whose records add up to more than the stage is packed in pieces of Rs reads.
-    uint32_t Rs = (stage_cap - 64) / rec;
-    if (Rs > (PK_THREADS - 1) / 4) Rs = (PK_THREADS - 1) / 4;   // 4R + 1 line offsets, one per lane
-    if (Rs == 0) Rs = 1;
-    uint32_t R = Rs;
-    const uint32_t avg = (uint32_t)hp->avg_record_bytes;        // 0 = unknown
-    if (avg >= 4 && avg < rec) {
-        R = (stage_cap - 64) / (avg + avg * 15 / 100 + 1);
-        if (R > (PK_THREADS - 1) / 4) R = (PK_THREADS - 1) / 4;
-        if (R < Rs) R = Rs;
-    }
-    // ... but the rows of a tile are sized for the LONGEST read: a file of short reads with a few long ones among them must not ask for
-    // R rows of the long kind in LDS (a request beyond the CU's 160 KiB ended the call with an error instead of a slower tile)
-    {
-        const uint32_t out_cap = stage_cap * 3 / 4, fit = out_cap / (Cd + Cq);
-        if (R > fit) R = fit > Rs ? fit : Rs;
-    }
-    // R a multiple of 16 keeps every tile's output offset 16-byte aligned (uint4 stores); when that would waste
-    // more than ~15 % of the tile, settle for a multiple of 8 or 4 (8- / 4-byte stores)
-    if (R >= 4) {
-        const uint32_t r16 = R & ~15u, r8 = R & ~7u, r4 = R & ~3u;
-        if (r16 * 100 >= R * 85) R = r16; else if (r8 * 100 >= R * 85) R = r8; else R = r4;
-    }
-    if (R == 0) R = 1;
-    if (Rs > R) Rs = R;
-    g.R = R; g.Rs = Rs;
-    g.stage_bytes = pk_stage_bytes(d_stats != nullptr);         // (= stage_cap + 32; the kernels take it as a constant)
-    g.out_bytes = (((R * Cd + 15) & ~15u) + R * Cq + 15) & ~15u;
-    // phase B: P lanes per read
-    uint32_t P = (d_q ? PK_THREADS - 64 : PK_THREADS) / R;        // (QN: the last wave parses QNAME lines instead)
-    if (P > g.G) P = g.G;
-    if (P < 1) P = 1;
-    g.P = P; g.magicP = magic_u32(P);
+    const uint32_t R = tg.R;
+    g.R = tg.R; g.Rs = tg.Rs;
+    g.stage_bytes = tg.stage_bytes;                             // (the kernels take it as a constant)
+    g.out_bytes = tg.out_bytes;
+    g.P = tg.P; g.magicP = magic_u32(tg.P);                     // phase B: P lanes per read
     // fast path: bases == "ACGT" (2 bits) or up to eight bases that three bits of their characters tell apart (3 bits), qualities one
     // contiguous ASCII range below 128, at most one N-trick base
     bool fast = bd == 2 && hp->dna_code['A'] == 0 && hp->dna_code['C'] == 1 && hp->dna_code['G'] == 2 && hp->dna_code['T'] == 3;
@@ -1173,15 +1185,16 @@ static int pack_impl(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* d_line_s
         return 0;
     }
     const bool var_deal = d_stats && use_lists && hp->variable;
-    const size_t lds_static = d_stats ? pks_words((int)bd, ntrick || d_q != nullptr) * 4 + ((ntrick || d_q != nullptr) ? ((sizeof(PkParked) + 15) & ~size_t(15)) : 0) : 4;        // the kernels' count table (and what they park beside it)
-    const size_t lds = 16 + (size_t)g.stage_bytes + g.out_bytes + (4 * R + 4) * 4 + 3 * 512 + (d_stats ? sizeof(QnLds) : 0);
+    const size_t lds_static = tg.lds_static;        // the kernels' count table (and what they park beside it)
+    const size_t lds = tg.lds_dynamic;
     UQ_REQUIRE(lds + lds_static <= 160 * 1024, "uq_pack: tile needs %zu bytes of LDS", lds + lds_static);
     const uint64_t tiles = (nreads + R - 1) / R;
-    PackKernel k = d_stats ? pick_stats_kernel((int)bd, (int)bq, ntrick, d_q != nullptr, use_lists, var_deal) : pick_kernel((int)bd, (int)bq, ntrick, fast);
+    PackKernel k = tg.tile64 ? pick_tile64((int)bq, ntrick, d_q != nullptr, use_lists)
+                 : d_stats ? pick_stats_kernel((int)bd, (int)bq, ntrick, d_q != nullptr, use_lists, var_deal) : pick_kernel((int)bd, (int)bq, ntrick, fast);
     if (lds > 48 * 1024) UQ_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // persistent workgroups: exactly as many as are resident at once (LDS and registers both limit that: a grid sized from the LDS
     // alone would leave the kernels built for four waves per SIMD with a second, quarter-full round of workgroups)
-    uint32_t per_cu = (uint32_t)((160 * 1024) / (lds + lds_static));
+    uint32_t per_cu = tg.wg_per_cu;
     {
         // (computed from the kernel's register count: hipOccupancyMaxActiveBlocksPerMultiprocessor is one workgroup per CU high for
         // kernels with 97-112 SGPRs on this ROCm -- MI355X_MICROARCH.md, Correctness boundaries -- which these are)
@@ -1237,6 +1250,14 @@ extern "C" int uq_pack_stats(uq_ctx* ctx, const uint8_t* d_buf, const uint64_t* 
                              uq_stats* d_stats, int* h_fused) {
     UQ_REQUIRE(d_stats && h_fused, "uq_pack_stats: null argument");
     return pack_impl(ctx, d_buf, d_line_start, first_read, nreads, h_guess, d_dna, d_qual, d_bad, d_stats, h_fused);
+}
+
+extern "C" int uq_pack_tile_geometry(const uq_pack_params* hp, uint32_t form, uq_pack_tile_geom* h_out) {
+    UQ_REQUIRE(hp && h_out, "uq_pack_tile_geometry: null argument");
+    UQ_REQUIRE((form & UQ_PACK_FORM_STATS) || !(form & (UQ_PACK_FORM_QNAME | UQ_PACK_FORM_LISTS)), "uq_pack_tile_geometry: the QNAME phase and the lists belong to the fused kernel");
+    const pkgeom::Geometry g = pkgeom::tile_geometry(pk_query(hp, (form & UQ_PACK_FORM_STATS) != 0, (form & UQ_PACK_FORM_QNAME) != 0, (form & UQ_PACK_FORM_LISTS) != 0));
+    *h_out = uq_pack_tile_geom{g.tiled, g.tile64, g.R, g.Rs, g.P, g.G, g.stage_bytes, g.out_bytes, g.copies, g.lds_bytes, g.wg_per_cu, 0u};
+    return 0;
 }
 
 // uq_pack_stats behind a census still in flight (uq_count_lines_end_async + uq_index_lines_async): the number of reads is taken on the

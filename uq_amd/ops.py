@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import call, Stats, PackParams, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, AdapterParams, AdapterReport, DedupParams, DedupReport, UQ_NONE, load
+from ._lib import call, Stats, PackParams, PackTileGeom, UnpackParams, SynthSpec, GzipStreamInfo, BgzfPart, Fingerprint, MateReport, FilterParams, FilterReport, TrimParams, TrimReport, AdapterParams, AdapterReport, DedupParams, DedupReport, UQ_NONE, load
 
 PATTERN_IDS = {'0.1': 0, '0.2': 1, '1.1': 2, '1.2': 3, '2.1': 4, '2.2': 5, '3.1': 6, '3.2': 7}
 
@@ -1024,6 +1024,15 @@ def same_pack_params(a, b):
     same = C.c_int(0)
     call('uq_same_pack_params', C.byref(a), C.byref(b), C.byref(same))
     return bool(same.value)
+
+
+def pack_tile_geometry(params, stats=True, qname=False, lists=False):
+    """The tile geometry the pack kernels run `params` at (uq_pack_tile_geometry; host only): a PackTileGeom -- tiled, tile64, R, Rs, P, G,
+    stage_bytes, out_bytes, copies, lds_bytes, wg_per_cu.  stats / qname / lists name the kernel: the fused pack + statistics form, its
+    QNAME phase, the line starts from the census's lists."""
+    g = PackTileGeom()
+    call('uq_pack_tile_geometry', C.byref(params), (1 if stats else 0) | (2 if qname else 0) | (4 if lists else 0), C.byref(g))
+    return g
 
 
 def same_pack_params_py(a, b):
